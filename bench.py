@@ -21,6 +21,12 @@ direction then runs ~64-byte requests and tops out ~20 % lower, profiles/zerocop
 ``--io device`` scores HBM-resident records (kernel-only; reported as an extra field too).  K steps are timed between a barrier +
 ``torch.cuda.synchronize()`` on both sides; the max over ranks is reported by rank 0 as ONE JSON
 line.  Weights are random-init (seeded), data is synthetic (no network, no checkpoints).
+
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds, after the
+timed steps, everything else measured here (the output check, the copy bound, kernel-only rate,
+16-byte records, DP training, collectives, GCN, route optimizer, serving latencies); without it
+those keys are null.  ``--dump-outputs DIR`` writes the last timed step's predictions as ``.npy``
+(same arguments, same inputs: two builds can be compared output for output).
 """
 from __future__ import annotations
 
@@ -78,7 +84,41 @@ def parse_args():
                     help="also time this many steps of the batched route optimizer (K5 + K6 + one "
                          "A* launch over MLP edge costs; extra JSON key 'route_optimizer'; skipped "
                          "on a shared GPU)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else this script measures or checks: "
+                         "the record-copy bound, the output check against the fp32 model and the bf16 "
+                         "emulation, kernel-only throughput, 16-byte records, DP training, collectives, "
+                         "GCN, the route optimizer and the serving latencies (their keys are null without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the predicted minutes of the last timed step to "
+                         "DIR/eta_minutes.npy (float32; DIR/eta_minutes_rank<r>.npy per rank when N > 1)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        # a plain run times the headline steps and nothing else
+        a.p50 = a.rec16_steps = a.gcn_steps = a.train_steps = a.route_steps = 0
+    return a
+
+
+#: --dump-outputs writes at most this many rows over all ranks (32 MB of float32)
+DUMP_ROWS = 1 << 23
+
+
+def dump_outputs(dirname: str, got, rank: int, world: int) -> None:
+    """Write the last timed step's predictions (what a caller of the timed path receives) as
+    float32 ``.npy``.  A batch larger than this rank's share of ``DUMP_ROWS`` is written as a fixed
+    sample: rows drawn once with a seeded generator, in ascending order, so two runs with the same
+    arguments write the same rows."""
+    import numpy as np
+    out = got.numpy().astype(np.float32, copy=False)
+    cap = DUMP_ROWS // world
+    if out.shape[0] > cap:
+        idx = np.sort(np.random.default_rng(20240 + rank).integers(0, out.shape[0], size=cap))
+        out = out[idx]
+    os.makedirs(dirname, exist_ok=True)
+    name = "eta_minutes.npy" if world == 1 else f"eta_minutes_rank{rank}.npy"
+    np.save(os.path.join(dirname, name), np.ascontiguousarray(out))
 
 
 def main() -> None:
@@ -259,7 +299,7 @@ def main() -> None:
 
     # the link bound: the record DMA alone, same bytes, same stream (what the step cannot beat)
     h2d_only_ms = None
-    if a.io == "hybrid":
+    if a.full and a.io == "hybrid":
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.stream(h2d_s):
             e0.record(h2d_s)
@@ -269,36 +309,42 @@ def main() -> None:
         torch.cuda.synchronize()
         h2d_only_ms = e0.elapsed_time(e1) / 10
 
-    # verify the headline kernel's own output from the last timed step (not a separate small
-    # launch): every row finite, and a 64k-row slice against the fp32 model and the bf16 emulation
-    # of the kernel on the same (wire-format-decoded) features
-    from routest_amd.ops.eta_mlp import emulate_kernel, featurize_torch
+    # the headline kernel's own output from the last timed step (not a separate small launch)
     got = pipe.last_output(a.warmup + a.steps - 1)
-    from routest_amd.utils.faults import active_faults
-    if "bench_corrupt_output" in active_faults():     # test hook: the check must catch this
-        got[0] = float("nan")
-        got[1:64] += 1e3
-    ok = bool(torch.isfinite(got).all().item())
-    nchk = min(B, 65536)
-    rec_chk = pipe.host_rec[:nchk]
-    with torch.no_grad():
-        ref32 = model.float().cpu()(featurize_torch(rec_chk)).reshape(-1)
-    emu = emulate_kernel(kern.packed.to("cpu"), rec_chk, kern._pick(B)).reshape(-1)
-    spread = float((ref32 - ref32.mean()).abs().mean()) + 1e-6
-    err_fp32 = float((got[:nchk] - ref32).abs().max()) / spread
-    err_emu = float((got[:nchk] - emu).abs().max()) / spread
-    ok = ok and err_emu < 0.05 and err_fp32 < 0.25
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, got, rank, world)
 
-    # device-only throughput of the fused kernel on the same batch (reported alongside)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(3):
-        kern(pipe.dev_rec[0])
-    ev0.record()
-    for _ in range(30):
-        kern(pipe.dev_rec[0])
-    ev1.record()
-    torch.cuda.synchronize()
-    kernel_preds_per_s = B * 30 / (ev0.elapsed_time(ev1) / 1e3)
+    ok, finite = True, None
+    err_fp32 = err_emu = kernel_preds_per_s = None
+    if a.full:
+        # verify that output: every row finite, and a 64k-row slice against the fp32 model and the
+        # bf16 emulation of the kernel on the same (wire-format-decoded) features
+        from routest_amd.ops.eta_mlp import emulate_kernel, featurize_torch
+        from routest_amd.utils.faults import active_faults
+        if "bench_corrupt_output" in active_faults():     # test hook: the check must catch this
+            got[0] = float("nan")
+            got[1:64] += 1e3
+        ok = bool(torch.isfinite(got).all().item())
+        nchk = min(B, 65536)
+        rec_chk = pipe.host_rec[:nchk]
+        with torch.no_grad():
+            ref32 = model.float().cpu()(featurize_torch(rec_chk)).reshape(-1)
+        emu = emulate_kernel(kern.packed.to("cpu"), rec_chk, kern._pick(B)).reshape(-1)
+        spread = float((ref32 - ref32.mean()).abs().mean()) + 1e-6
+        err_fp32 = float((got[:nchk] - ref32).abs().max()) / spread
+        err_emu = float((got[:nchk] - emu).abs().max()) / spread
+        ok = finite = ok and err_emu < 0.05 and err_fp32 < 0.25
+
+        # device-only throughput of the fused kernel on the same batch (reported alongside)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(3):
+            kern(pipe.dev_rec[0])
+        ev0.record()
+        for _ in range(30):
+            kern(pipe.dev_rec[0])
+        ev1.record()
+        torch.cuda.synchronize()
+        kernel_preds_per_s = B * 30 / (ev0.elapsed_time(ev1) / 1e3)
 
     # the same pipeline on full 16-byte records (epoch seconds: weekday/hour resolved by the
     # kernel itself, float age and distance — no lossy packing), reported as an extra key
@@ -441,7 +487,7 @@ def main() -> None:
     # whole-node runs: what the xGMI links delivered, measured on the same ranks right after the
     # timed region (RCCL all-reduce / all-gather sweep; extra JSON key, outside the timing)
     coll = None
-    if world > 1 and not share and os.environ.get("ROUTEST_BENCH_COLLECTIVES", "1") != "0":
+    if a.full and world > 1 and not share and os.environ.get("ROUTEST_BENCH_COLLECTIVES", "1") != "0":
         # RCCL on the process group bench.py already holds, plus the one-shot all-reduce when its
         # set-up and training probe succeeded on every rank: every decision here depends only on
         # state all ranks agreed on, so no rank can be left waiting on a step another one skipped
@@ -749,7 +795,8 @@ def main() -> None:
             "serving_error": serving_error,
             "check_max_err_vs_emulation": err_emu,
             "check_max_err_vs_fp32": err_fp32,
-            "finite": ok,
+            "finite": finite,
+            "full": bool(a.full),
         }
         out["schema_problems"] = bench_schema.problems(out)
         print(json.dumps(out), flush=True)

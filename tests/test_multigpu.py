@@ -178,7 +178,7 @@ def test_bench_launches_all_gpus():
     env.pop("WORLD_SIZE", None)
     if SHARE:
         env["ROUTEST_BENCH_SHARE_GPU"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), "--steps", "3",
                         "--warmup", "1", "--batch", "1048576", "--p50", "0", "--rec16-steps", "2",
                         "--route-requests", "2000", "--route-steps", "1"],
                        capture_output=True, text=True, timeout=400, cwd=ROOT, env=env)

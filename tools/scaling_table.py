@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Scaling table from ``bench.py`` JSON lines run at several GPU counts (one line per N, e.g.
-``for n in 1 2 4 8; do python bench.py --gpus $n; done > scale.jsonl``).
+``for n in 1 2 4 8; do python bench.py --full --gpus $n; done > scale.jsonl``).
 
 Prints a markdown table per config the line carries: the headline (config 2, inference sharding),
 DP training at 64k and 1M rows per GPU over RCCL and over the one-shot all-reduce (config 3), the GCN
