@@ -90,9 +90,6 @@ class PyCchGpu {
     d["triangle_table"] = g_->has_triangle_table();
     d["triangles"] = g_->triangles();
     d["basic_tasks"] = g_->basic_tasks();
-    d["basic_tail_levels"] = g_->basic_tail_levels();
-    d["perfect_tail_levels"] = g_->perfect_tail_levels();
-    d["perfect_tasks"] = g_->perfect_tasks();
     d["supernodal"] = g_->supernodal();
     d["sup_fronts"] = g_->sup_fronts();
     d["sup_nodes"] = g_->sup_nodes();

@@ -1,6 +1,6 @@
-// GPU customizable contraction hierarchy (csrc/cch.hip): customization per routing context and
-// batched elimination-tree queries.  Host preprocessing and the bit-identical CPU reference:
-// csrc/runtime/cch.h.
+// GPU customizable contraction hierarchy: customization per routing context (csrc/cch_customize.hip),
+// batched elimination-tree queries (csrc/cch_query.hip), construction, metric cache and background
+// builders (csrc/cch.hip).  Host preprocessing and the bit-identical CPU reference: csrc/runtime/cch.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -88,7 +88,6 @@ struct CustScratch {
   void* rec_buf = nullptr;                         // context cost records [2E]
   float* min_buf = nullptr;                        // their minutes [2E]
   float* h_stage = nullptr;                        // pinned [E]: the costs' host copy lands here first
-  int* tail_ctl = nullptr;                         // basic_tail_kernel: cursor, timed-out flag, done[level]
   unsigned long long* sup_buf = nullptr;           // dense fronts of one supernode level (build_supernodes)
 };
 
@@ -128,13 +127,12 @@ class CchGpu {
   const rcch::Topology& topo() const { return T_; }
   int device() const { return dev_; }
   int stride() const { return T_.max_depth + 1; }
-  bool has_triangle_table() const { return d_tri != nullptr; }
+  // the accelerated customization (triangle table, basic tasks, pull records) or, when its tables
+  // do not fit ROUTEST_CCH_TRI_GB, the fallback (level kernels with binary searches)
+  bool has_triangle_table() const { return accel_; }
   int64_t triangles() const { return n_tri; }
   int64_t basic_tasks() const { return n_btask_; }
-  int basic_tail_levels() const { return n_tail_lev_; }   // top basic levels run by ONE persistent launch
-  int perfect_tail_levels() const { return n_ptail_lev_; }  // top perfect depths run by ONE persistent launch
-  int64_t perfect_tasks() const { return n_ptask_; }
-  // supernodal customization of the etree's top (csrc/cch.hip build_supernodes; ROUTEST_CCH_DENSE)
+  // supernodal customization of the etree's top (csrc/cch_customize.hip build_supernodes; ROUTEST_CCH_DENSE)
   bool supernodal() const { return sup_on_; }
   int sup_fronts() const { return sup_fronts_; }
   int sup_nodes() const { return sup_nodes_; }
@@ -259,35 +257,34 @@ class CchGpu {
   float* d_length = nullptr;
   uint8_t *d_class = nullptr, *d_base_traffic = nullptr;
   int32_t *d_hnodes = nullptr, *d_dnodes = nullptr;
-  int64_t *d_bofs = nullptr, *d_pofs = nullptr;    // work-item prefixes in level order
-  int64_t* d_aofs = nullptr;                       // arc prefix in depth order (perfect pull)
-  void* d_parc = nullptr;                          // per depth-ordered arc: csrc/cch.hip PArc
-  std::vector<int64_t> bofs_, pofs_, aofs_;        // host copies (level boundaries)
+  int64_t *d_bofs = nullptr, *d_pofs = nullptr;    // work-item prefixes in level order (fallback kernels)
+  std::vector<int64_t> bofs_, pofs_, aofs_;        // host: item / arc prefixes (level boundaries)
   std::vector<int> plev_kmax_;                     // widest node (upward arcs) per depth level
+  // The customization runs one of two paths, chosen once by the constructor (csrc/cch_customize.hip
+  // build_tables).  Accelerated: every table below exists.  Fallback (a table did not fit the
+  // ROUTEST_CCH_TRI_GB budget or could not be built): none does, the level kernels search instead.
+  bool accel_ = false;
+  void build_tables();
+  void free_tables();
   // triangle table (metric-independent): for the pair (i < j) of rank z's upward arcs, the arc id of
   // {head i, head j} at tri[tofs[z] + i(2k-i-1)/2 + j-i-1] — the customization's binary searches
-  // done once per graph (nullptr when it would not fit the ROUTEST_CCH_TRI_GB budget)
-  int64_t* d_tofs = nullptr;
+  // done once per graph
+  bool build_triangles(const std::vector<int64_t>& tofs);
   int32_t* d_tri = nullptr;
   int64_t n_tri = 0;
-  // task tables of the customization (csrc/cch.hip build_tasks): 8-byte wave tasks in level order
-  void build_tasks(const std::vector<int64_t>& tofs);
-  void build_pull_records(const std::vector<int64_t>& tofs);
+  // the basic phase's 24-byte wave tasks in height order, and the perfect pull's per-arc records in
+  // depth order (csrc/cch_customize.hip BasicTask, PArc)
+  bool build_tasks(const std::vector<int64_t>& tofs);
+  bool build_pull_records(const std::vector<int64_t>& tofs);
   void* d_btask = nullptr;
-  void* d_ptask = nullptr;
-  std::vector<int64_t> btask_ptr_, ptask_ptr_;
-  int64_t n_btask_ = 0, n_ptask_ = 0;
-  // the basic phase's narrow top (levels h_tail_ .. max_height, each <= ROUTEST_CCH_TAIL tasks):
-  // basic_tail_kernel, d_tail_end_[l] = end of tail level l's tasks (relative to h_tail_'s first)
-  int h_tail_ = -1, n_tail_lev_ = 0, tail_max_tasks_ = 0;
-  int* d_tail_end_ = nullptr;
-  // ... and of the perfect phase (depths 0 .. n_ptail_lev_ - 1): perfect_tail_kernel over their arcs
-  int n_ptail_lev_ = 0, ptail_max_arcs_ = 0;
-  int* d_ptail_end_ = nullptr;
-  // supernodal top: the chains of at least ROUTEST_CCH_DENSE nodes and every ancestor chain are dense
-  // fronts, customized level by level of the supernode tree (csrc/cch.hip sup_*_kernel); the rest of
-  // the nodes keep the per-level kernels (basic: the task table without the fronts' nodes; perfect:
-  // the pull over d_parc2, by depth below the nearest front)
+  std::vector<int64_t> btask_ptr_;
+  int64_t n_btask_ = 0;
+  void* d_parc = nullptr;
+  // supernodal top (optional on the accelerated path): the chains of at least ROUTEST_CCH_DENSE nodes
+  // and every ancestor chain are dense fronts, customized level by level of the supernode tree
+  // (csrc/cch_customize.hip sup_*_kernel); the rest of the nodes keep the per-level kernels (basic:
+  // the task table without the fronts' nodes; perfect: the pull over d_parc2, by depth below the
+  // nearest front)
   void build_supernodes(const std::vector<int64_t>& tofs);
   struct SupRange {
     int64_t off = 0, cnt = 0;
@@ -314,6 +311,12 @@ class CchGpu {
   // one set per background builder (no lock: each builder owns its set)
   hipError_t alloc_scratch(CustScratch& x);
   void free_scratch(CustScratch& x);
+  // the phases of customize(), in order on stream s (max_wg > 0: a paced background build, wide
+  // levels launched in pieces of at most max_wg workgroups)
+  hipError_t reset_weights(hipStream_t s, CustScratch& x, CchMetricDev& m);
+  hipError_t basic_phase(hipStream_t s, CustScratch& x, CchMetricDev& m, int max_wg);
+  hipError_t perfect_phase(hipStream_t s, CustScratch& x, CchMetricDev& m, int max_wg);
+  hipError_t prune_phase(hipStream_t s, CustScratch& x, CchMetricDev& m);
   CustScratch cs0_;
   std::vector<std::unique_ptr<CustScratch>> bscr_;
   std::mutex mu_cust_;

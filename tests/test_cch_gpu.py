@@ -135,7 +135,7 @@ def test_bulk_route_step_reuse_matches_fresh_sweeps(setup, monkeypatch):
 
 def test_paced_background_build_bit_identical_to_cpu(setup):
     """A context built by the background builders with pacing (wide levels launched in pieces of
-    16 workgroups, csrc/cch.hip customize) gives the CPU reference's answers bit for bit."""
+    16 workgroups, csrc/cch_customize.hip customize) gives the CPU reference's answers bit for bit."""
     import time
     from routest_amd.routing.cch import RouteContext
     g, m, router, cost, key, cpu, mc = setup
@@ -162,29 +162,41 @@ def test_paced_background_build_bit_identical_to_cpu(setup):
     assert all(np.array_equal(a, b) for a, b in zip(paths, p2))
 
 
-@pytest.mark.parametrize("tail", ["64", "4096"])
-def test_persistent_tails_bit_identical_to_cpu(setup, monkeypatch, tail):
-    """ROUTEST_CCH_TAIL: the narrow top levels of both phases in one persistent launch each
-    (basic_tail_kernel / perfect_tail_kernel: work queue + bounded level waits) give the same bits
-    as the per-level launches and the CPU reference."""
+def test_no_triangle_table_fallback_bit_identical(monkeypatch):
+    """ROUTEST_CCH_TRI_GB=0: without the triangle table the customization is the fallback path
+    (basic_level_kernel / perfect_level_kernel, binary searches).  Its metric arrays equal the
+    accelerated path's bit for bit, and its answers the CPU reference's."""
+    from routest_amd import _rt
     from routest_amd.routing.cch import RoadRouter
-    g, m, router, cost, key, cpu, mc = setup
-    monkeypatch.setenv("ROUTEST_CCH_TAIL", tail)
-    monkeypatch.setenv("ROUTEST_CCH_DENSE", "0")      # (the tails are the per-level path's top)
-    r2 = RoadRouter(g, m, device="cuda:0")
-    st = r2.stats()
-    assert st["basic_tail_levels"] > 0 and st["perfect_tail_levels"] > 0, st
-    key2 = r2.metric_from_costs(1 << 41, cost)
-    src, dst = synth_route_queries(g, 2000, seed=3)
-    a = r2.route(src, dst, key2, want_path=False)
+    g = synth_road_graph(20_000, seed=5)
+    m = default_model(hidden=64, steps=50)
+    cost = edge_costs(g, m, device="cuda:0")
+    ra = RoadRouter(g, m, device="cuda:0")
+    st = ra.stats()
+    assert st["triangle_table"] and st["supernodal"], st
+    monkeypatch.setenv("ROUTEST_CCH_TRI_GB", "0")
+    rb = RoadRouter(g, m, device="cuda:0")
+    st = rb.stats()
+    assert not st["triangle_table"] and not st["supernodal"], st
+    ka = ra.metric_from_costs(1 << 40, cost)
+    kb = rb.metric_from_costs(1 << 40, cost)
+    da = {k: v.cpu() for k, v in ra.gpu.metric_dump(ka).items()}
+    db = {k: v.cpu() for k, v in rb.gpu.metric_dump(kb).items()}
+    assert da.keys() == db.keys()
+    for name, ref in da.items():
+        assert torch.equal(db[name], ref), name
+    cpu = _rt.CCH(g.indptr, g.indices, g.lat, g.lon, 0)
+    mc = cpu.customize(cost, g.length_m)
+    src, dst = synth_route_queries(g, 1000, seed=3)
+    a = rb.route(src, dst, kb, want_path=False)
     b = cpu.query(mc, src, dst, False)
     for x, y in zip(a[:3], b[:3]):
         assert np.array_equal(np.asarray(x), np.asarray(y))
 
 
 def test_supernodal_fronts_bit_identical_to_per_level(setup, monkeypatch):
-    """ROUTEST_CCH_DENSE: the dense-front customization of the elimination tree's top (csrc/cch.hip
-    sup_*_kernel: blocked (min, +) elimination / back substitution per chain) gives the per-level
+    """ROUTEST_CCH_DENSE: the dense-front customization of the elimination tree's top
+    (csrc/cch_customize.hip sup_*_kernel: blocked (min, +) elimination / back substitution per chain) gives the per-level
     kernels' metric arrays bit for bit — with no fronts (0), every chain a front (1), only long chains
     (32) and the default — and so the CPU reference's answers (the other tests here run the default)."""
     from routest_amd.routing.cch import RoadRouter

@@ -1,4 +1,4 @@
-"""The supernodal customization's algebra on the CPU (numpy emulation of csrc/cch.hip sup_*): basic
+"""The supernodal customization's algebra on the CPU (numpy emulation of csrc/cch_customize.hip sup_*): basic
 customization as blocked tropical elimination of dense fronts and perfect customization as blocked
 back substitution give the per-node reference results BIT for bit — packed (weight, middle) words
 for basic, f32 weights for perfect — on a small synthetic graph's CCH (csrc/runtime/cch.h topology).

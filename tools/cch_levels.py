@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Work per elimination-tree level of the CCH customization (csrc/cch.hip): how many levels the
+"""Work per elimination-tree level of the CCH customization (csrc/cch_customize.hip): how many levels the
 basic (by height) and perfect (by depth) phases have, and how their items are distributed — the
 input for choosing which levels run in the one-workgroup persistent kernel and which get a full
 grid launch.  Usage: ``python tools/cch_levels.py [nodes] [--json out]``."""
