@@ -81,6 +81,10 @@ CchGpu::CchGpu(rcch::Topology T, const float* length, const uint8_t* road_class,
   if (base_traffic) ck(up_copy(d_base_traffic, base_traffic, E));
   ck(up_copy(d_hnodes, T_.hlev_nodes.data(), N));
   ck(up_copy(d_dnodes, T_.dlev_nodes.data(), N));
+  {
+    std::vector<int32_t> dlev32(T_.dlev_ptr.begin(), T_.dlev_ptr.end());
+    ck(up_copy(d_dlev_ptr, dlev32.data(), dlev32.size()));
+  }
   ck(up_copy(d_bofs, bofs_.data(), N + 1));
   ck(up_copy(d_pofs, pofs_.data(), N + 1));
 
@@ -123,6 +127,7 @@ CchGpu::~CchGpu() {
   dfree(d_base_traffic);
   dfree(d_hnodes);
   dfree(d_dnodes);
+  dfree(d_dlev_ptr);
   dfree(d_bofs);
   dfree(d_pofs);
   free_tables();

@@ -58,6 +58,7 @@ class PyCchGpu {
                                       host_ptr<uint8_t>(road_class, E, "road_class"),
                                       host_ptr<uint8_t>(base_traffic, E, "base_traffic"), dev_);
     sc_ = std::make_unique<rt::CchScratch>();
+    asc_ = std::make_unique<rt::CchAllScratch>();
   }
 
   void set_eta(torch::Tensor blob, int64_t H, std::vector<double> norm, int64_t variant) {
@@ -326,6 +327,27 @@ class PyCchGpu {
     return py::make_tuple(sec, met, st, len, path);
   }
 
+  // one-to-all (reverse: all-to-one): src int32 [S] node ids -> (sec, metres) float32 [S, N] by node
+  // id, +inf where unreachable.  Its own scratch: a live matrix_keep tag stays valid.  fuse: see
+  // CchGpu::one_to_all (< 0: the default schedule).
+  py::tuple one_to_all(int64_t key, torch::Tensor src, bool reverse, int64_t fuse) {
+    auto m = get(key);
+    TORCH_CHECK(src.is_cuda() && src.device().index() == dev_ && src.scalar_type() == torch::kInt32 &&
+                    src.is_contiguous() && src.dim() == 1,
+                "src: int32 [S] on the router's GPU");
+    const int64_t S = src.numel();
+    const int64_t N = g_->topo().N;
+    TORCH_CHECK(S < ((int64_t)1 << 31) - 64, "too many sources");
+    if (S > 0) TORCH_CHECK(src.min().item<int>() >= 0 && src.max().item<int>() < N, "node id out of range");
+    auto of = torch::TensorOptions().dtype(torch::kFloat32).device(torch::kCUDA, dev_);
+    auto sec = torch::empty({S, N}, of), met = torch::empty({S, N}, of);
+    const c10::DeviceGuard guard(src.device());
+    std::lock_guard<std::mutex> lk(mu_);
+    CCH_CHECK_HIP(g_->one_to_all(*m, src.data_ptr<int>(), (int)S, reverse, sec.data_ptr<float>(), met.data_ptr<float>(),
+                                 *asc_, stream_of(dev_), (int)fuse));
+    return py::make_tuple(sec, met);
+  }
+
   void set_capacity(int64_t n) { g_->set_capacity((int)n); }
   uintptr_t ptr() const { return reinterpret_cast<uintptr_t>(g_.get()); }
   py::dict topology_arrays() const {
@@ -337,6 +359,7 @@ class PyCchGpu {
       return t;
     };
     d["rank"] = i32(T.rank);
+    d["node"] = i32(T.node);
     d["parent"] = i32(T.parent);
     d["depth"] = i32(T.depth);
     d["up_head"] = i32(T.up_head);
@@ -368,6 +391,7 @@ class PyCchGpu {
 
   std::unique_ptr<rt::CchGpu> g_;
   std::unique_ptr<rt::CchScratch> sc_;
+  std::unique_ptr<rt::CchAllScratch> asc_;
   std::mutex mu_;
   torch::Tensor blob_;
   int dev_ = 0;
@@ -397,6 +421,8 @@ void bind_cch_gpu(py::module& m) {
       .def("matrix_keep", &PyCchGpu::matrix_keep, py::arg("key"), py::arg("pts"), py::arg("npts"))
       .def("legs_from_matrix", &PyCchGpu::legs_from_matrix, py::arg("key"), py::arg("tag"), py::arg("pts"), py::arg("r"),
            py::arg("i"), py::arg("j"), py::arg("max_path") = 4096, py::arg("want_path") = true)
+      .def("one_to_all", &PyCchGpu::one_to_all, py::arg("key"), py::arg("src"), py::arg("reverse") = false,
+           py::arg("fuse") = -1)
       .def("set_capacity", &PyCchGpu::set_capacity)
       .def("set_cache_gb", &PyCchGpu::set_cache_gb, py::arg("gb"))
       .def("set_builder_pacing", &PyCchGpu::set_builder_pacing, py::arg("max_workgroups"), py::arg("always") = false)

@@ -77,6 +77,19 @@ struct CchScratch {
   hipError_t ensure(size_t jobs, size_t pairs, int stride, int max_arcs);
 };
 
+// Work labels of one-to-all calls (csrc/cch_all.hip): seconds and metres as [blocks][N][64] in rank
+// space, 64 sources per block on the lane axis.  Its own struct: a one_to_all call leaves a
+// CchScratch (and the matrix chains a legs_from_matrix tag points at) alone.
+struct CchAllScratch {
+  float* sec = nullptr;
+  float* met = nullptr;
+  size_t blocks_cap = 0;
+  int device = 0;
+  std::vector<void*> old;          // outgrown buffers, freed with the scratch
+  ~CchAllScratch();
+  hipError_t ensure(size_t blocks, size_t N);
+};
+
 // Device temporaries of one customization (the up/down arc weights with middles, the perfect
 // pass's packed words, the prune counts, the scan's temp, the context-cost records and minutes).
 struct CustScratch {
@@ -223,6 +236,18 @@ class CchGpu {
                               int Q, uint64_t tag, const CchRouteOut& o, CchScratch& sc, hipStream_t s);
   static constexpr int MAX_ARCS = 1024;   // shortcut arcs per path before unpacking
 
+  // one-to-all (csrc/cch_all.hip; CPU reference rcch::one_to_all, bit-identical): d_src [S] node ids
+  // on the device -> d_sec / d_met [S][N] by node id, +inf where unreachable; reverse: all-to-one,
+  // the times TO each source.  The sources are processed in chunks of 64-source blocks whose work
+  // labels fit ALL_SCRATCH_BYTES (the 1M-node city: 512 MB per block, two blocks per chunk).
+  // fuse: runs of consecutive depth levels of at most this many nodes go to ONE launch (a workgroup
+  // per source block, a barrier between levels) instead of a launch per level; 0: a launch per
+  // level; < 0: the default (ROUTEST_CCH_ALL_FUSE, else ALL_FUSE_WIDTH).
+  hipError_t one_to_all(const CchMetricDev& m, const int* d_src, int S, bool reverse, float* d_sec, float* d_met,
+                        CchAllScratch& sc, hipStream_t s, int fuse = -1);
+  static constexpr size_t ALL_SCRATCH_BYTES = 1ull << 30;
+  static constexpr int ALL_FUSE_WIDTH = 4;
+
   // The same over several metrics at once: d_mv [G] views (view(m), on the device), d_grp the
   // metric of each leg (route, legs_from_matrix) or request row (matrix).  Bit-identical per leg to
   // the single-metric calls.
@@ -257,6 +282,7 @@ class CchGpu {
   float* d_length = nullptr;
   uint8_t *d_class = nullptr, *d_base_traffic = nullptr;
   int32_t *d_hnodes = nullptr, *d_dnodes = nullptr;
+  int32_t* d_dlev_ptr = nullptr;                   // [max_depth + 2] T_.dlev_ptr (one-to-all's fused levels)
   int64_t *d_bofs = nullptr, *d_pofs = nullptr;    // work-item prefixes in level order (fallback kernels)
   std::vector<int64_t> bofs_, pofs_, aofs_;        // host: item / arc prefixes (level boundaries)
   std::vector<int> plev_kmax_;                     // widest node (upward arcs) per depth level

@@ -745,4 +745,60 @@ inline void query(const Topology& T, const Metric& m, int32_t s_node, int32_t t_
     if (!unpack_arc(T, m, bw[i], 1, out.path, max_path)) { out.status = 4; out.path.clear(); return; }
 }
 
+// ------------------------------------------------------------------------------------------------
+// One-to-all (isochrones): every node's time-shortest seconds from rank s and the metres of that
+// path, in RANK space (sec / met: [N]).  The chain of s is swept upward once over the kept forward
+// arcs, then every rank in non-decreasing etree depth pulls from the heads of its kept backward
+// arcs (all of them ancestors, so already final).  reverse: the two record sets and len_up / len_dn
+// swap roles and the labels are the all-to-one times TO s.
+//
+// A candidate replaces a label iff it is lexicographically smaller — fewer seconds, or equal
+// seconds and fewer metres.  That minimum does not depend on the order the candidates arrive in,
+// so the GPU kernels (csrc/cch_all.hip) give the same bits under any schedule.  It is NOT the pair
+// query's tie rule (deepest meeting depth): on equal-seconds ties the metres may legitimately
+// differ from query(); and the seconds are sums grown from the source only, where query() adds two
+// sums grown from both ends, so they agree to rounding, not bit for bit.
+inline bool label_less(float s1, float m1, float s0, float m0) { return s1 < s0 || (s1 == s0 && m1 < m0); }
+
+inline void one_to_all(const Topology& T, const Metric& m, int32_t s, bool reverse, float* sec, float* met) {
+  const int N = T.N;
+  std::fill(sec, sec + N, INF);
+  std::fill(met, met + N, INF);
+  sec[s] = 0.f;
+  met[s] = 0.f;
+  const std::vector<int64_t>& uptr = reverse ? m.b_ptr : m.f_ptr;
+  const std::vector<int32_t>& uarc = reverse ? m.b_arc : m.f_arc;
+  const std::vector<float>& uw = reverse ? m.b_w : m.f_w;
+  const std::vector<float>& ulen = reverse ? m.len_dn : m.len_up;
+  const std::vector<int64_t>& dptr = reverse ? m.f_ptr : m.b_ptr;
+  const std::vector<int32_t>& darc = reverse ? m.f_arc : m.b_arc;
+  const std::vector<float>& dw = reverse ? m.f_w : m.b_w;
+  const std::vector<float>& dlen = reverse ? m.len_up : m.len_dn;
+  for (int32_t x = s; x >= 0; x = T.parent[x]) {
+    if (!(sec[x] < INF)) continue;
+    for (int64_t k = uptr[x]; k < uptr[x + 1]; ++k) {
+      const int32_t a = uarc[k], u = T.up_head[a];
+      const float cs = sec[x] + uw[k], cm = met[x] + ulen[a];
+      if (label_less(cs, cm, sec[u], met[u])) {
+        sec[u] = cs;
+        met[u] = cm;
+      }
+    }
+  }
+  for (int32_t v : T.dlev_nodes) {
+    float bs = sec[v], bm = met[v];
+    for (int64_t k = dptr[v]; k < dptr[v + 1]; ++k) {
+      const int32_t a = darc[k], u = T.up_head[a];
+      if (!(sec[u] < INF)) continue;
+      const float cs = sec[u] + dw[k], cm = met[u] + dlen[a];
+      if (label_less(cs, cm, bs, bm)) {
+        bs = cs;
+        bm = cm;
+      }
+    }
+    sec[v] = bs;
+    met[v] = bm;
+  }
+}
+
 }  // namespace rcch

@@ -139,6 +139,38 @@ class PyCCH {
     return py::make_tuple(sec, met, st, want_path ? py::object(paths) : py::object(py::none()));
   }
 
+  // one-to-all (reverse: all-to-one): (sec f32[S, N], metres f32[S, N]) by node id, +inf where
+  // unreachable; the sources run in parallel on the pool.  The label rule (lexicographic min of
+  // (seconds, metres), rcch::one_to_all) is not query()'s deepest-meeting-depth rule: on
+  // equal-seconds ties the metres may differ from query(), and seconds agree to rounding only.
+  py::tuple one_to_all(const PyMetric& pm, arr<int32_t> sources, bool reverse) {
+    if (sources.ndim() != 1) throw std::invalid_argument("sources: int32 [S]");
+    const py::ssize_t S = sources.shape(0);
+    const int32_t* s = sources.data();
+    for (py::ssize_t i = 0; i < S; ++i)
+      if (s[i] < 0 || s[i] >= T_.N) throw std::out_of_range("source node out of range");
+    const py::ssize_t N = T_.N;
+    py::array_t<float> sec({S, N}), met({S, N});
+    float* ps = sec.mutable_data();
+    float* pmet = met.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      pool_.run((size_t)S, [&](size_t i) {
+        thread_local std::vector<float> ls, lm;
+        ls.resize((size_t)N);
+        lm.resize((size_t)N);
+        rcch::one_to_all(T_, *pm.m, T_.rank[s[i]], reverse, ls.data(), lm.data());
+        float* os = ps + i * (size_t)N;
+        float* om = pmet + i * (size_t)N;
+        for (py::ssize_t r = 0; r < N; ++r) {
+          os[T_.node[r]] = ls[r];
+          om[T_.node[r]] = lm[r];
+        }
+      });
+    }
+    return py::make_tuple(sec, met);
+  }
+
   // timing-only batch (the CPU baseline): queries without paths or with paths, returns wall ms
   double bench(const PyMetric& pm, arr<int32_t> src, arr<int32_t> dst, bool want_path) {
     const py::ssize_t Q = src.shape(0);
@@ -201,6 +233,7 @@ void bind_cch(py::module& m) {
       .def("customize", &PyCCH::customize, py::arg("cost"), py::arg("length"))
       .def("query", &PyCCH::query, py::arg("metric"), py::arg("src"), py::arg("dst"), py::arg("want_path") = true,
            py::arg("max_path") = 1 << 20)
+      .def("one_to_all", &PyCCH::one_to_all, py::arg("metric"), py::arg("sources"), py::arg("reverse") = false)
       .def("bench", &PyCCH::bench, py::arg("metric"), py::arg("src"), py::arg("dst"), py::arg("want_path") = false)
       .def("metric_arrays", &PyCCH::metric_arrays);
 }

@@ -501,6 +501,27 @@ def create_app(services: Optional[Services] = None, settings: Optional[Settings]
             return JSONResponse({"error": f"invalid route: {e}"}, 400)
         return JSONResponse(res, 200)
 
+    @app.post("/api/isochrones")
+    async def isochrones(request: Request):
+        """What each location reaches within each range under the request's context (ORS's
+        isochrones shape; routing/isochrone.py): a FeatureCollection, one MultiPolygon Feature per
+        (location, range)."""
+        body = await _json_body(request, silent=False)
+        if isinstance(body, Response):
+            return body
+        if getattr(sv.provider, "name", "") != "graph" or not hasattr(sv.provider, "reachable"):
+            return JSONResponse({"error": "isochrones need the road graph: start the service with "
+                                          "ROUTEST_PROVIDER=graph"}, 400)
+        from ..routing.cch import RouteContext
+        from ..routing.isochrone import isochrones as _isochrones
+        from ..routing.providers import ProviderError
+        try:
+            res = await run_in_threadpool(_isochrones, sv.provider, body, RouteContext.from_request(body),
+                                          sv.route_device)
+        except (ValueError, ProviderError) as e:
+            return JSONResponse({"error": str(e)}, 400)
+        return JSONResponse(res, 200)
+
     # ------------------------------------------------------------------ ETA
     async def _predict_one(body: Dict[str, Any]):
         summary = body.get("summary") or {}

@@ -272,6 +272,23 @@ class RoadRouter:
         np.fill_diagonal(met, 0.0)
         return sec, met
 
+    def one_to_all(self, sources: Sequence[int], ctx_or_key, reverse: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """(seconds, metres) [S, N] from every source to every node id (``reverse``: from every
+        node TO the source); unreachable = inf.  One upward chain sweep per source and one
+        top-down pass over the hierarchy (csrc/cch_all.hip; CPU: ``_rt.CCH.one_to_all``, the
+        bit-identical reference).  Metres are those of the time-shortest path, ties between
+        equal-seconds paths going to the shorter one — not :meth:`route`'s tie rule, so on such a
+        tie the metres may differ from a leg's; seconds agree with legs to f32 rounding."""
+        with self.pinned(ctx_or_key) as key:
+            s = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+            if len(s) and (s.min() < 0 or s.max() >= self.g.num_nodes):
+                raise IndexError("source node out of range")
+            if self.gpu is not None:
+                sec, met = self.gpu.one_to_all(key, torch.from_numpy(s).to(self.dev), bool(reverse))
+                return sec.cpu().numpy(), met.cpu().numpy()
+            sec, met = self.cpu.one_to_all(self._cpu_metrics[key], s, bool(reverse))
+            return np.asarray(sec), np.asarray(met)
+
     def matrices(self, node_lists: Sequence[Sequence[int]], ctx_or_key) -> List[Tuple[np.ndarray, np.ndarray]]:
         """Many requests' matrices at once (ONE sweep + meet launch on the GPU)."""
         with self.pinned(ctx_or_key) as key:

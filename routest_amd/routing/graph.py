@@ -627,6 +627,51 @@ class GraphProvider(HaversineProvider):
             _, met = self.router().matrix(list(map(int, nodes)), key)
         return met.astype(np.float64)
 
+    def _street_edges(self):
+        """(tail, head, metres) of every street once: a two-way street's two directed edges count
+        as one (the lower -> higher node id one), a one-way street's only edge as itself."""
+        with self._lock:
+            if getattr(self, "_streets", None) is None:
+                g = self.g
+                n = np.int64(g.num_nodes)
+                u = np.repeat(np.arange(g.num_nodes, dtype=np.int64), np.diff(g.indptr))
+                v = g.indices.astype(np.int64)
+                once = (u < v) | ((u > v) & ~np.isin(v * n + u, u * n + v))
+                self._streets = (u[once], v[once], g.length_m[once].astype(np.float64))
+            return self._streets
+
+    def reachable(self, points: List[Dict[str, float]], ranges: Sequence[float], range_type: str = "time",
+                  reverse: bool = False, ctx=None, device=None) -> List[Dict[str, Any]]:
+        """What each point reaches within each range (isochrones; ORS's third routing primitive).
+
+        ``points`` are snapped to graph nodes and answered by ONE one-to-all call of the CCH router
+        under the request's context.  ``range_type`` ``"time"``: seconds of the time-shortest path;
+        ``"distance"``: the metres of that same time-shortest path (the semantics :meth:`matrix`
+        documents), not a distance-shortest search.  ``reverse``: what reaches the point instead.
+        One dict per (point, range), points outermost: ``point`` / ``range`` (indices), ``value``,
+        ``node`` (the snapped node), ``nodes`` (reached node ids, ascending), ``values`` (their
+        seconds or metres), ``reached_nodes`` and ``reach_m`` (metres of the streets with both ends
+        reached, each street once)."""
+        if self.engine == "astar":
+            raise ProviderError("isochrones need the CCH router: ROUTEST_ROUTER=astar has no one-to-all search "
+                                "(unset it or use ROUTEST_ROUTER=cch)")
+        if range_type not in ("time", "distance"):
+            raise ValueError("range_type must be 'time' or 'distance'")
+        nodes = self.g.nearest_nodes([p["lat"] for p in points], [p["lon"] for p in points])
+        with self.pinned_metric(ctx, device) as key:
+            sec, met = self.router(device).one_to_all(np.asarray(nodes, dtype=np.int32), key, reverse=reverse)
+        val = sec if range_type == "time" else met
+        eu, ev, em = self._street_edges()
+        out = []
+        for i in range(len(nodes)):
+            for j, rg in enumerate(ranges):
+                mask = val[i] <= np.float32(rg)
+                ids = np.flatnonzero(mask).astype(np.int32)
+                out.append({"point": i, "range": j, "value": float(rg), "node": int(nodes[i]), "nodes": ids,
+                            "values": val[i][ids], "reached_nodes": int(len(ids)),
+                            "reach_m": float(em[mask[eu] & mask[ev]].sum())})
+        return out
+
     def directions(self, coords: List[List[float]], profile: str, ctx=None) -> Dict[str, Any]:
         nodes, pairs = self.leg_pairs(coords)
         with self.pinned_metric(ctx) as key:
