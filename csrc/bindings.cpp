@@ -1185,8 +1185,8 @@ static std::shared_ptr<const rt::NativeModel> model_from(const py::dict& d, int 
                 " must be contiguous on GPU ", device);
     return t;
   };
-  const c10::DeviceGuard guard(c10::Device(c10::DeviceType::CUDA, device));
   if (kind == "mlp3") {
+    const c10::DeviceGuard guard(c10::Device(c10::DeviceType::CUDA, device));
     torch::Tensor blob = dev_t("blob");
     const int H = d["H"].cast<int>();
     TORCH_CHECK(blob.scalar_type() == torch::kUInt8 && (size_t)blob.numel() == rt::eta_mlp3_blob_bytes(H), "mlp3 blob");
@@ -1194,6 +1194,7 @@ static std::shared_ptr<const rt::NativeModel> model_from(const py::dict& d, int 
                             d.contains("variant") ? d["variant"].cast<int>() : -1, num_cus(device), mlp_host_from(d),
                             err);
   } else if (kind == "wide") {
+    const c10::DeviceGuard guard(c10::Device(c10::DeviceType::CUDA, device));
     torch::Tensor w1q = dev_t("w1q"), w2f = dev_t("w2f"), b2 = dev_t("b2"), w3 = dev_t("w3");
     const int H = d["H"].cast<int>();
     TORCH_CHECK(b2.scalar_type() == torch::kFloat32 && w3.scalar_type() == torch::kFloat32 && b2.numel() == H &&
@@ -1202,6 +1203,8 @@ static std::shared_ptr<const rt::NativeModel> model_from(const py::dict& d, int 
                             b2.data_ptr<float>(), w3.data_ptr<float>(), d["b3"].cast<float>(), norm_from(d),
                             mlp_host_from(d), err);
   } else if (kind == "forest") {
+    // host arrays only: make_forest_model checks them before it touches the device (and selects
+    // the device for its copies itself), so a bad forest is refused without a GPU
     rt::ForestHost f;
     torch::Tensor v = d["values"].cast<torch::Tensor>().to(torch::kCPU).contiguous();
     torch::Tensor in = d["info"].cast<torch::Tensor>().to(torch::kCPU).contiguous();

@@ -220,6 +220,8 @@ std::shared_ptr<NativeModel> make_wide_model(int device, int H, const void* w1q,
   return m;
 }
 
+constexpr int FOREST_MAX_DEPTH = 64;   // forest.hip: a walk takes at most 64 steps (`guard++ < 64`)
+
 std::shared_ptr<NativeModel> make_forest_model(int device, ForestHost host, std::string& err) {
   const size_t M = host.values.size();
   if (M == 0 || host.info.size() != M || host.roots.empty() || host.roots[0] != 0) {
@@ -240,6 +242,35 @@ std::shared_ptr<NativeModel> make_forest_model(int device, ForestHost host, std:
       if (((inf >> 24) & 63) >= 12 || b + (inf & 0xFFFFFF) + 1 >= e) {
         err = "forest: node reference out of range";
         return nullptr;
+      }
+    }
+  }
+  // at most FOREST_MAX_DEPTH inner nodes on a root-to-leaf path: the kernels stop a walk after that
+  // many steps (forest.py validate).  Level k = the nodes a walk can stand on after k steps; a
+  // cycle never empties the frontier and is refused as well.
+  {
+    std::vector<int> seen(M, -1);
+    std::vector<uint32_t> cur, nxt;
+    for (size_t t = 0; t < host.roots.size(); ++t) {
+      const uint32_t b = (uint32_t)host.roots[t];
+      cur.assign(1, b);
+      for (int level = 0; !cur.empty(); ++level) {
+        nxt.clear();
+        for (uint32_t n : cur) {
+          const uint32_t inf = host.info[n];
+          if (inf >> 31) continue;
+          if (level == FOREST_MAX_DEPTH) {
+            err = "forest: tree " + std::to_string(t) + " is deeper than the kernels' depth limit of " +
+                  std::to_string(FOREST_MAX_DEPTH) + " inner nodes on a root-to-leaf path";
+            return nullptr;
+          }
+          for (uint32_t c = b + (inf & 0xFFFFFF), e = c + 2; c < e; ++c)
+            if (seen[c] != level) {
+              seen[c] = level;
+              nxt.push_back(c);
+            }
+        }
+        cur.swap(nxt);
       }
     }
   }

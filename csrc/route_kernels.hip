@@ -10,7 +10,7 @@
 // K6 greedy_cvrp_kernel: ONE WAVEFRONT PER REQUEST.  Reference semantics (see
 //    routest_amd/routing/greedy.py): candidates are scanned once per trip in the (stable) order of
 //    their distance from the depot; a candidate is accepted iff load + demand <= cap and
-//    trip_dist + d[cur][i] + d[i][0] <= max_dist.  Sequential in the reference; here each
+//    trip_dist + (d[cur][i] + d[i][0]) <= max_dist.  Sequential in the reference; here each
 //    acceptance is one parallel step: the 64 lanes test the candidates after the current scan
 //    position, a 64-bit ballot finds the FIRST feasible one in scan order (exactly the one the
 //    sequential scan would accept next, since everything before it was rejected under the same
@@ -29,6 +29,10 @@ __global__ __launch_bounds__(256) void haversine_matrix_kernel(const double* __r
                                                                const int* __restrict__ npts, int R,
                                                                int NM, double circuity,
                                                                double* __restrict__ D) {
+  // No FMA contraction, like the host's haversine_m (runtime/route_core.h): fused into
+  // fma(lon_j, k, -(lon_i * k)), the difference of two EQUAL products is the rounding error of the
+  // product instead of 0, and two parcels for one address came out ~2e-9 m apart.
+#pragma clang fp contract(off)
   const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long total = (long long)R * NM * NM;
   if (tid >= total) return;

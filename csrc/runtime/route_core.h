@@ -1077,7 +1077,8 @@ inline bool greedy_trips(const std::vector<double>& d, int n1, const std::vector
     for (int idx : order) {
       if (vis[idx]) continue;
       const double dm = dem[idx];
-      if ((load + dm) <= cap && (tdist + d[(size_t)cur * n1 + idx] + d[(size_t)idx * n1]) <= maxd) {
+      // the reference's association: added = d[cur][idx] + d[idx][0] first, then tdist + added
+      if ((load + dm) <= cap && (tdist + (d[(size_t)cur * n1 + idx] + d[(size_t)idx * n1])) <= maxd) {
         trip.push_back(idx);
         load += dm;
         tdist += d[(size_t)cur * n1 + idx];

@@ -170,16 +170,37 @@ class ForestModel:
         idx = np.searchsorted(self.roots, node, side="right") - 1
         return self.roots[idx]
 
+    MAX_DEPTH = 64         # csrc/forest.hip: a walk takes at most 64 steps (`guard++ < 64`)
+
     def validate(self) -> None:
-        """Host check of the packed format (children in range, features < 12) before any launch."""
+        """Host check of the packed format before any launch: children inside their own tree,
+        features < 12, and at most MAX_DEPTH inner nodes on any root-to-leaf path (the kernels stop
+        a walk after that many steps; csrc/native_model.hip make_forest_model checks the same)."""
         M = len(self.values)
-        if len(self.info) != M or not len(self.roots) or self.roots[0] != 0 or np.any(np.diff(self.roots) <= 0):
+        if (len(self.info) != M or not len(self.roots) or self.roots[0] != 0 or np.any(np.diff(self.roots) <= 0)
+                or self.roots[-1] >= M):
             raise ValueError("malformed forest arrays")
         inner = (self.info >> 31) == 0
         idx = np.nonzero(inner)[0]
-        child = self.roots_offset(idx) + (self.info[idx] & 0xFFFFFF).astype(np.int64)
-        if np.any(child + 1 >= M) or np.any(((self.info[idx] >> 24) & 63) >= 12):
+        tree = np.searchsorted(self.roots, idx, side="right") - 1
+        end = np.append(self.roots[1:], M).astype(np.int64)[tree]
+        child = self.roots[tree] + (self.info[idx] & 0xFFFFFF).astype(np.int64)
+        if np.any(child + 1 >= end) or np.any(((self.info[idx] >> 24) & 63) >= 12):
             raise ValueError("forest node references out of range")
+        # level k = the nodes a walk can stand on after k steps; an inner node there is the
+        # (k+1)-th inner node of some path.  A cycle never empties the frontier and is refused too.
+        left = np.full(M, -1, dtype=np.int64)
+        left[idx] = child
+        frontier = self.roots.astype(np.int64)
+        for _ in range(self.MAX_DEPTH):
+            lo = left[frontier]
+            lo = lo[lo >= 0]
+            if not len(lo):
+                return
+            frontier = np.unique(np.concatenate([lo, lo + 1]))
+        if np.any(left[frontier] >= 0):
+            raise ValueError(f"forest tree deeper than the kernels' depth limit of {self.MAX_DEPTH} "
+                             "inner nodes on a root-to-leaf path")
 
     def device_arrays(self, device):
         import torch

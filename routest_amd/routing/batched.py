@@ -73,6 +73,13 @@ def _unpack(visit: np.ndarray, trip_of: np.ndarray, ntrips: np.ndarray, status: 
 
 def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device,
                          D: Optional[np.ndarray] = None) -> List[TripsOrError]:
+    # K6 indexes its LDS order / visited arrays by stop number: a request longer than the padded
+    # width would write past them, so it is refused here, before anything reaches the device
+    nm = int(D.shape[1]) if D is not None else int(np.shape(lat)[1])
+    n = np.asarray(npts)
+    if n.size and (int(n.min()) < 0 or int(n.max()) > nm):
+        raise ValueError(f"npts must lie in 0..{nm} (the padded width of the batch), got "
+                         f"{int(n.min())}..{int(n.max())}")
     C = _ext.native(required=True)
     dev = torch.device(device)
     t = lambda a, dt=torch.float64: torch.as_tensor(a, dtype=dt).to(dev)  # noqa: E731

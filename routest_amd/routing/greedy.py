@@ -1,13 +1,19 @@
 """Capacity- and distance-constrained multi-trip greedy construction (R21) — CPU reference.
 
-Exact semantics of ``RO/Flaskr/utils.py:111-139``::
+Semantics of ``RO/Flaskr/utils.py:111-139``::
 
     while unvisited:
         trip=[0]; load=0; trip_dist=0; current=0
         for idx in sorted(unvisited, key=lambda i: d[current][i]):   # sorted() runs ONCE, current==0
-            if load+demand<=cap and trip_dist + d[current][idx] + d[idx][0] <= max_dist:
+            added = d[current][idx] + d[idx][0]
+            if load+demand<=cap and trip_dist + added <= max_dist:
                 accept: trip.append(idx); load+=demand; trip_dist+=d[current][idx]; current=idx
         trip.append(0); remove trip's stops from unvisited
+
+The fp64 sum is associated as the reference writes it, ``trip_dist + (d[current][idx] + d[idx][0])``:
+``(trip_dist + a) + b`` can differ by one ulp and flip the ``<=`` when ``max_dist`` sits on that
+boundary.  :func:`greedy_trips`, the C++ runtime (``csrc/runtime/rt.cpp``, ``route_core.h``) and the
+GPU kernel all use this association, so they return the reference's trips on every feasible input.
 
 Note the subtlety the survey's "nearest-first" hides: ``sorted`` is evaluated once per trip while
 ``current`` is still the depot, so candidates are scanned in order of distance *from the depot*
@@ -49,7 +55,7 @@ def greedy_trips(d: Sequence[Sequence[float]], demand: Sequence[float], cap: flo
             if visited[idx]:
                 continue
             dem = float(demand[idx])
-            if (load + dem) <= cap and (trip_dist + d[cur][idx] + d[idx][0]) <= max_dist:
+            if (load + dem) <= cap and (trip_dist + (d[cur][idx] + d[idx][0])) <= max_dist:
                 trip.append(idx)
                 load += dem
                 trip_dist += d[cur][idx]

@@ -170,6 +170,45 @@ def test_forest_served_natively_matches_cpu_reference():
         st.close()
 
 
+@pytest.mark.parametrize("le", [False, True])
+def test_synthetic_forest_served_natively_is_exact(le):
+    """make_forest_model + launch_forest (csrc/native_model.hip, forest.hip forest_kernel) behind
+    the native front end, on a synthetic forest whose sums are exact in f32 (tests/_forest_synth.py:
+    integer leaves, thresholds drawn from the requests' own feature values): the served minutes
+    equal the numpy reference exactly, through the native port and through the app."""
+    from _forest_synth import TreeGen
+    from routest_amd.models.features import RECORD_DTYPE, records_to_features
+    from routest_amd.models.forest import ForestModel
+    from routest_amd.serve.eta_service import EtaService
+    items = [{"summary": {"distance": [0, 1000, 2500, 500.5, 12345.678, 99999][i % 6]},
+              "pickup_time": f"2025-08-{20 + i % 9:02d}T{(5 * i) % 24:02d}:30:00",
+              "weather": ["Cloudy", "Stormy", "Sunny", "Windy", "Foggy"][i % 5],
+              "traffic": ["High", "Jam", "Low", "Medium", "Unknown"][(i // 5) % 5],
+              "driver_age": [18, 30, 45.5, 64][(i // 3) % 4]} for i in range(300)]
+    rec = np.array([EtaService.make_record(weather=it["weather"], traffic=it["traffic"],
+                                           distance_m=float(it["summary"]["distance"]), pickup_time=it["pickup_time"],
+                                           driver_age=float(it["driver_age"]))[0] for it in items], dtype=RECORD_DTYPE)
+    x = records_to_features(rec)
+    g = TreeGen(x, 21)
+    trees = [g.tree(s) for s in [("leaf",), ("chain", 64), ("grow", 200, 3, 12), ("full", 6), ("chain", 7)]
+             + [("grow", 30, 2, 8)] * 30]
+    fm = ForestModel._pack(trees, 5.0, le, list(range(12)))
+    want = [float(v) for v in fm.predict_features(x)]
+    flipped = ForestModel._pack(trees, 5.0, not le, list(range(12))).predict_features(x)
+    assert np.mean(flipped != np.asarray(want, np.float32)) >= 0.10      # `<` for `<=` would show
+    st, sv = _stack(fm)
+    try:
+        assert st.front is not None and "forest" in st.front.health()["slots"][0]["model"]
+        a = _req(st.port, "POST", "/predict", items)
+        b = _req(st.app_server.port, "POST", "/predict", items)
+        assert a[0] == b[0] == 200
+        assert [p["eta_minutes_ml"] for p in json.loads(a[1])["predictions"]] == want
+        assert [p["eta_minutes_ml"] for p in json.loads(b[1])["predictions"]] == want
+        assert st.front.stats()["predictions"] >= 300            # answered natively
+    finally:
+        st.close()
+
+
 @pytest.mark.run_first
 def test_hung_gpu_slot_watchdog_and_route_failover():
     """Verdict r4 item 5 / SURVEY §5.3 "a watchdog on batch latency": with gpu_hang@1 (slot 1's

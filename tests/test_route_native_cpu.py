@@ -72,6 +72,38 @@ def test_haversine_requests_byte_identical():
     assert n == 2000
 
 
+def test_native_greedy_uses_the_reference_association():
+    """route_core.h greedy_trips (reached through route_optimize_cpu) on requests whose
+    maximum_distance separates `trip_dist + (a + b)` from `(trip_dist + a) + b`: the trips are the
+    literal reference loop's on the same matrix, and the body is the Python app's byte for byte."""
+    from _greedy_cases import _feasible, differs
+    from routest_amd.routing.greedy import greedy_trips_reference_literal, optimized_order
+    prov = HaversineProvider()
+    rng = np.random.default_rng(7)
+    n_trips = {1: 0, 2: 0}
+    for _ in range(4000):
+        pts = [{"lat": float(14.55 + rng.normal(0, 0.05)), "lon": float(121.02 + rng.normal(0, 0.05))} for _ in range(3)]
+        d = [[0.0 if i == j else rt.haversine_m(p["lat"], p["lon"], q["lat"], q["lon"]) * 1.3 for j, q in enumerate(pts)]
+             for i, p in enumerate(pts)]
+        t, a, b = d[0][1], d[1][2], d[2][0]
+        if not (t <= d[0][2] and differs(t, a, b)):
+            continue
+        maxd = min((t + a) + b, t + (a + b))
+        inst = (d, [0.0, 1.0, 1.0], 10.0, maxd)
+        if not _feasible(inst):
+            continue
+        ref = greedy_trips_reference_literal(*inst)
+        p = {"source_point": pts[0], "destination_points": [dict(q, payload=1) for q in pts[1:]],
+             "driver_details": {"vehicle_capacity": 10, "maximum_distance": maxd}}
+        body = json.dumps(p).encode()
+        st, out = rt.route_optimize_cpu(body)
+        props = json.loads(out)["properties"]
+        assert st == 200 and props["summary"]["trips"] == len(ref) and props["optimized_order"] == optimized_order(ref)
+        assert (st, out) == _python(json.loads(body), prov)
+        n_trips[len(ref)] += 1
+    assert min(n_trips.values()) >= 20, n_trips
+
+
 def test_silent_body_and_request_route_semantics():
     # optimize_route (silent JSON): a non-JSON body or a non-dict reads as {}
     for body, ok in ((b"not json", False), (b"[1,2]", True), (b"null", True), (b"", True)):

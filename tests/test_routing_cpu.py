@@ -40,6 +40,43 @@ def test_greedy_matches_reference_literal_random():
     assert checked > 300
 
 
+def test_greedy_association_of_the_distance_sum():
+    """The reference tests `trip_dist + (d[cur][idx] + d[idx][0]) <= max_dist`.  On instances whose
+    max_dist separates that sum from `(trip_dist + d[cur][idx]) + d[idx][0]` (tests/_greedy_cases.py),
+    greedy_trips, the C++ runtime's greedy_trips and the literal reference loop return the same
+    trips.  Equality of trip lists: nothing here has a tolerance."""
+    from _greedy_cases import association_instances
+    from routest_amd.ops import _ext
+    rt = _ext.runtime(required=True)
+    d = [[0, .1, .3], [.1, 0, .2], [.3, .2, 0]]
+    assert greedy_trips_reference_literal(d, [0, 1, 1], 10, 0.6) == [[0, 1, 2, 0]]
+    assert greedy_trips(d, [0, 1, 1], 10, 0.6) == [[0, 1, 2, 0]]
+    insts = association_instances()
+    assert len(insts) >= 60
+    one_trip = 0
+    for d, dem, cap, maxd in insts:
+        ref = greedy_trips_reference_literal(d, dem, cap, maxd)
+        assert greedy_trips(d, dem, cap, maxd) == ref
+        got, rest = rt.greedy_trips(np.asarray(d, dtype=np.float64), [float(q) for q in dem], float(cap), float(maxd))
+        assert rest is None and got == ref
+        one_trip += len(ref) == 1
+    # both directions: the reference's sum is the smaller one (it alone accepts) and the larger one
+    assert 10 <= one_trip <= len(insts) - 10
+
+
+def test_batched_device_refuses_npts_beyond_the_padded_width():
+    """K6 indexes per-request LDS arrays by stop number: npts > NM must never reach a launch.  The
+    check runs on the host before the extension is even loaded."""
+    from routest_amd.routing.batched import batched_trips_device
+    lat = np.zeros((2, 3)); dem = np.zeros((2, 3))
+    for npts in ([3, 4], [-1, 2]):
+        with pytest.raises(ValueError, match="padded width"):
+            batched_trips_device(lat, lat, dem, np.array(npts, np.int32), np.ones(2), np.ones(2), 1.3, "cuda:0")
+        with pytest.raises(ValueError, match="padded width"):
+            batched_trips_device(lat, lat, dem, np.array(npts, np.int32), np.ones(2), np.ones(2), 1.3, "cuda:0",
+                                 D=np.zeros((2, 3, 3)))
+
+
 def test_greedy_sort_is_by_depot_distance():
     # The reference's sorted() is evaluated once per trip with current == 0, so the scan order is by
     # distance from the DEPOT, not from the current stop (utils.py:125).
