@@ -13,6 +13,7 @@
 #include "ops.h"
 #include "runtime/route_core.h"
 #include "runtime/route_record.h"
+#include "runtime/route_store.h"
 
 #include <mutex>
 
@@ -141,12 +142,9 @@ struct RouteJob {
   std::vector<rtr::Leg> alt_legs;
   std::vector<std::vector<int32_t>> alt_paths, alt_edges;
   std::string alt_json;
-  rtr::Assembled asmb;
-  float eta_min = NAN;
-  std::string eta_iso, request_id;
-  std::string p_stops, p_geom;      // row texts for the persistence thread (prep_persist)
-  std::string rec;                  // compact route record (route_record.h; "" = legs / geometry as text)
-  bool p_ok = false;
+  // the assembled response, its compact route record, the ETA and — once persisted — the request
+  // id, with the row texts the persistence thread binds (runtime/route_store.h; row.root = req.root)
+  rts::StoreRow row;
   rtc::Stamp now;
 };
 

@@ -7,6 +7,8 @@
 //    R21 greedy, directions, assembly) -> (status, body) or None (fallback to Python) — the CPU
 //    reference the GPU service is tested against, and a fast path for GPU-less deployments.
 //  * route_assemble_graph: graph-provider assembly from given trips + searched legs (tests).
+//  * RouteStore / RowId: the route service's SQLite writer (route_store.h) over requests assembled
+//    by the two functions above (as_row=True) — its CPU tests.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -19,6 +21,7 @@
 #include "history_db.h"
 #include "route_core.h"
 #include "route_record.h"
+#include "route_store.h"
 
 namespace py = pybind11;
 
@@ -210,10 +213,20 @@ std::pair<int, std::string> finish_plain(const rtr::Assembled& a, bool request_r
   return {200, a.body + "}}"};
 }
 
-py::object route_optimize_cpu(py::bytes body, bool json_ok, const std::string& engine, double circuity,
-                              double step_m, bool is_request_route, bool compat200) {
-  const std::string b = body;
+// One request assembled on the CPU as a row for the native writer (route_store.h): the body and
+// its parsed root stay with the row (StoreRow::root points into this object, which pybind11 keeps
+// on the heap).
+struct PyRouteRow {
+  std::string body;
   Value root;
+  rts::StoreRow row;
+};
+
+// false: the request is one for the Python app (-> None)
+bool optimize_cpu(PyRouteRow& o, bool json_ok, const std::string& engine, double circuity, double step_m,
+                  bool is_request_route) {
+  const std::string& b = o.body;
+  Value& root = o.root;
   bool parsed = false;
   if (json_ok && !b.empty()) {
     try {
@@ -222,13 +235,13 @@ py::object route_optimize_cpu(py::bytes body, bool json_ok, const std::string& e
     } catch (const std::exception&) {
     }
   }
-  if (is_request_route && (!json_ok || (!parsed && !b.empty()))) return py::none();   // 415 / 400: Python
-  Value empty;
-  empty.kind = Value::Obj;
+  if (is_request_route && (!json_ok || (!parsed && !b.empty()))) return false;   // 415 / 400: Python
+  static const Value empty = [] { Value v; v.kind = Value::Obj; return v; }();
   const Value* rootp = parsed ? &root : (is_request_route ? nullptr : &empty);
   if (!is_request_route && parsed && root.kind != Value::Obj) rootp = &empty;   // silent: non-dict -> {}
   rtr::RouteReq r = rtr::parse_route_request(rootp);
-  if (r.fallback || r.alt_k > 0) return py::none();     // alternatives: graph provider + scorer only
+  if (r.fallback || r.alt_k > 0) return false;     // alternatives: graph provider + scorer only
+  o.row.root = rootp;
   rtr::Plan plan;
   if (r.error.empty() && r.dst.size() > 1) {
     const int n1 = (int)r.dst.size() + 1;
@@ -250,25 +263,37 @@ py::object route_optimize_cpu(py::bytes body, bool json_ok, const std::string& e
   std::vector<rtr::Dir> dirs(calls.size());
   for (size_t k = 0; k < calls.size(); ++k)
     rtr::haversine_directions(calls[k], r.profile, circuity, step_m, dirs[k]);
-  rtr::Assembled a;
-  if (!rtr::assemble(r, plan, dirs, engine, a)) return py::none();
-  auto res = finish_plain(a, compat200, is_request_route);
+  return rtr::assemble(r, plan, dirs, engine, o.row.asmb);
+}
+
+py::object route_optimize_cpu(py::bytes body, bool json_ok, const std::string& engine, double circuity,
+                              double step_m, bool is_request_route, bool compat200, bool as_row) {
+  auto o = std::make_unique<PyRouteRow>();
+  o->body = body;
+  if (!optimize_cpu(*o, json_ok, engine, circuity, step_m, is_request_route)) return py::none();
+  if (as_row) return py::cast(std::move(o));
+  auto res = finish_plain(o->row.asmb, compat200, is_request_route);
   return py::make_tuple(res.first, to_bytes(res.second));
 }
 
 // Graph-provider assembly with given trips and searched legs: `trips` per request as index lists
 // (None for point-to-point), `legs` {(s, t): (seconds, [nodes]) | (seconds, metres, [nodes])}
 // (missing / empty = not found); with `steps` (GraphSteps) + `cost` the segments carry maneuvers.
+// as_row: the assembled request (and its record, with_record) as a row for RouteStore.
 py::object route_assemble_graph(py::bytes body, const std::string& engine,
                                 py::array_t<double, py::array::c_style | py::array::forcecast> glat,
                                 py::array_t<double, py::array::c_style | py::array::forcecast> glon,
                                 py::array_t<int32_t, py::array::c_style | py::array::forcecast> nodes_of_calls,
                                 py::object trips_obj, py::dict legs_obj, py::object steps_obj, py::object cost_obj,
-                                bool with_record) {
-  const std::string b = body;
-  Value root = rtj::Parser(b.data(), b.size()).parse();
+                                bool with_record, bool as_row) {
+  auto o = std::make_unique<PyRouteRow>();
+  o->body = body;
+  const std::string& b = o->body;
+  Value& root = o->root;
+  root = rtj::Parser(b.data(), b.size()).parse();
   rtr::RouteReq r = rtr::parse_route_request(&root);
   if (r.fallback) return py::none();
+  o->row.root = &root;
   rtr::Plan plan;
   if (!trips_obj.is_none()) plan.trips = trips_obj.cast<std::vector<std::vector<int>>>();
   std::vector<std::vector<std::pair<double, double>>> calls;
@@ -331,15 +356,51 @@ py::object route_assemble_graph(py::bytes body, const std::string& engine,
     }
     if (rec_ok) rec_ok = !sd.bad && rrec::add_call(rw, *rg, ghp, calls[k], legs, durs, per_leg);
   }
-  rtr::Assembled a;
+  rtr::Assembled& a = o->row.asmb;
   if (!rtr::assemble(r, plan, dirs, engine, a)) return py::none();
+  if (rec_ok && a.ok) o->row.rec = std::move(rw.b);
+  if (as_row) return py::cast(std::move(o));
   auto res = finish_plain(a, true, false);
   if (!with_record) return py::make_tuple(res.first, to_bytes(res.second));
   // (status, body, record bytes or None, the row's legs text, the row's geometry text)
   std::string geo = "{\"type\":\"LineString\",\"coordinates\":" + a.coords + "}";
-  return py::make_tuple(res.first, to_bytes(res.second), rec_ok && a.ok ? py::object(to_bytes(rw.b)) : py::object(py::none()),
-                        a.segments, geo);
+  return py::make_tuple(res.first, to_bytes(res.second),
+                        rec_ok && a.ok ? py::object(to_bytes(o->row.rec)) : py::object(py::none()), a.segments, geo);
 }
+
+// The native writer over a database the Python store created: the given rows committed as ONE
+// group -> their request ids ("" = not stored).  `etas`: per row None or (eta_min, eta_iso).
+class PyRouteStore {
+ public:
+  explicit PyRouteStore(const std::string& path) {
+    if (!s_.open(path)) throw std::runtime_error("RouteStore: cannot open " + path);
+  }
+  std::vector<std::string> commit(std::vector<PyRouteRow*> rows, py::object etas) {
+    std::vector<rts::StoreRow*> g;
+    for (size_t i = 0; i < rows.size(); ++i) {
+      rts::StoreRow& r = rows[i]->row;
+      r.eta_min = NAN;
+      r.eta_iso.clear();
+      if (!etas.is_none() && !etas.cast<py::list>()[i].is_none()) {
+        const auto eta = etas.cast<py::list>()[i].cast<std::pair<float, std::string>>();
+        r.eta_min = eta.first;
+        r.eta_iso = eta.second;
+      }
+      r.ok = false;               // as the service: only an assembled route is stored
+      if (r.root != nullptr && r.asmb.ok) rts::RouteStore::prepare(r);
+      g.push_back(&r);
+    }
+    {
+      py::gil_scoped_release nogil;
+      s_.commit_group(g);
+    }
+    std::vector<std::string> ids;
+    for (rts::StoreRow* r : g) ids.push_back(r->request_id);
+    return ids;
+  }
+ private:
+  rts::RouteStore s_;
+};
 
 using F64 = py::array_t<double, py::array::c_style | py::array::forcecast>;
 using I32 = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
@@ -382,10 +443,15 @@ void bind_route(py::module& m) {
       .def("nearest", &PyNodeGrid::nearest);
   m.def("route_optimize_cpu", &route_optimize_cpu, py::arg("body"), py::arg("json_ok") = true,
         py::arg("engine") = "backend:mi355x", py::arg("circuity") = 1.3, py::arg("step_m") = 150.0,
-        py::arg("is_request_route") = false, py::arg("compat200") = true);
+        py::arg("is_request_route") = false, py::arg("compat200") = true, py::arg("as_row") = false);
   m.def("route_assemble_graph", &route_assemble_graph, py::arg("body"), py::arg("engine"), py::arg("glat"),
         py::arg("glon"), py::arg("nodes"), py::arg("trips"), py::arg("legs"), py::arg("steps") = py::none(),
-        py::arg("cost") = py::none(), py::arg("with_record") = false);
+        py::arg("cost") = py::none(), py::arg("with_record") = false, py::arg("as_row") = false);
+  py::class_<PyRouteRow>(m, "RouteRow");
+  py::class_<PyRouteStore>(m, "RouteStore")
+      .def(py::init<const std::string&>(), py::arg("path"))
+      .def("commit", &PyRouteStore::commit, py::arg("rows"), py::arg("etas") = py::none());
+  py::class_<rts::RowId>(m, "RowId").def(py::init<>()).def("row_id", [](rts::RowId& r, uint64_t ms) { return r.next(ms); });
   m.def("py_round", &rtr::py_round);
   m.def("json_float", [](double v) {     // the native JSON writer's float (tests: == json.dumps)
     std::string o;

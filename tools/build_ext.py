@@ -58,8 +58,8 @@ def _run(cmd: List[str]) -> None:
 
 NO_SLP = {"eta_mlp_fwd.hip"}
 # host code that must round exactly like Python (csrc/runtime/route_core.h): no FMA contraction
-NO_CONTRACT = {"native_server.hip", "route_service.hip", "cch.hip", "cch_customize.hip", "cch_query.hip",
-               "cch_all.hip"}
+NO_CONTRACT = {"native_server.hip", "route_service.hip", "route_service_plan.hip", "route_service_legs.hip",
+               "cch.hip", "cch_customize.hip", "cch_query.hip", "cch_all.hip"}
 # builtin MFMAs write VGPRs: train_bwd_kernel pins its 256 dW2 accumulators to the AGPRs (inline-asm
 # MFMAs), and with the default heuristic the builtin MFMAs beside them also took AGPR destinations,
 # which made the allocator park accumulator tiles in VGPRs and copy them around every MFMA
