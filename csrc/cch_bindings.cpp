@@ -130,6 +130,8 @@ class PyCchGpu {
   }
   void set_cache_gb(double gb) { g_->set_cache_gb(gb); }
   void set_builder_pacing(int n, bool always) { g_->set_builder_pacing(n, always); }
+  void set_unpack_serial(bool on) { g_->set_unpack_serial(on); }
+  bool unpack_serial() const { return g_->unpack_serial(); }
 
   py::dict info(const rt::CchMetricDev& m, bool fresh) const {
     py::dict d;
@@ -426,6 +428,8 @@ void bind_cch_gpu(py::module& m) {
       .def("set_capacity", &PyCchGpu::set_capacity)
       .def("set_cache_gb", &PyCchGpu::set_cache_gb, py::arg("gb"))
       .def("set_builder_pacing", &PyCchGpu::set_builder_pacing, py::arg("max_workgroups"), py::arg("always") = false)
+      .def("set_unpack_serial", &PyCchGpu::set_unpack_serial, py::arg("on"))
+      .def("unpack_serial", &PyCchGpu::unpack_serial)
       .def("request_build", &PyCchGpu::request_build, py::arg("weather"), py::arg("congestion"), py::arg("weekhour"),
            py::arg("driver_age") = 35.0, py::arg("urgent") = true)
       .def("is_cached", &PyCchGpu::is_cached, py::arg("key"))

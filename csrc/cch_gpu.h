@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -121,8 +123,11 @@ struct CchMView {
 };
 
 struct CchRouteOut {
-  float* sec = nullptr;            // [Q] seconds (-1 when not found)
-  float* metres = nullptr;         // [Q] metres of the chosen path
+  // [Q] seconds and metres of the chosen path: the route's for status 0 and for a status 4 set by
+  // the unpack kernels (max_path); -1 for status 1 and for a path over the meet kernel's own
+  // arc-list limits (MAX_ARCS, a status 4 the CPU reference cannot produce)
+  float* sec = nullptr;
+  float* metres = nullptr;
   int* status = nullptr;           // [Q] 0 found, 1 unreachable, 4 too long / unpack overflow
   int* len = nullptr;              // [Q] path nodes
   int* path = nullptr;             // [Q, max_path] node ids (nullptr: costs only)
@@ -209,6 +214,10 @@ class CchGpu {
     pace_always_.store(always);
   }
   int builder_pacing() const { return builder_max_wg_.load(); }
+  // expand every path with the serial unpack kernel instead of the cooperative one (a test and
+  // diagnosis hook like set_builder_pacing, read per call; default: ROUTEST_CCH_UNPACK=serial)
+  void set_unpack_serial(bool on) { unpack_serial_.store(on); }
+  bool unpack_serial() const { return unpack_serial_.load(); }
   // a query flush ran now (the route services call this per flush): builds starting within the next
   // 250 ms are paced
   void note_queries() {
@@ -387,6 +396,10 @@ class CchGpu {
   std::atomic<int> builder_max_wg_{[] {
     const char* v = std::getenv("ROUTEST_CCH_BUILDER_MAX_WG");
     return v ? std::max(0, std::atoi(v)) : -1;
+  }()};
+  std::atomic<bool> unpack_serial_{[] {
+    const char* v = std::getenv("ROUTEST_CCH_UNPACK");
+    return v != nullptr && std::strcmp(v, "serial") == 0;
   }()};
 };
 

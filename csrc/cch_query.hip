@@ -9,9 +9,6 @@
 // deepest tie) and lists the shortcut arcs of the chosen up-down path; the unpack kernels expand them
 // to road nodes (cooperatively, 16 lanes per pair; a serial DFS per lane for the longest arc lists).
 // Many-to-many matrices reuse each point's two chains, and legs can reuse a matrix call's chains.
-#include <cstdlib>
-#include <string>
-
 #include "cch_dev.h"
 #include "cch_gpu.h"
 
@@ -594,10 +591,7 @@ hipError_t CchScratch::ensure(size_t J, size_t P, int stride, int max_arcs) {
 
 hipError_t CchGpu::launch_unpack(const CchMetricDev* m, const CchMView* mv, const int* grp, int Q, const int* d_src,
                                  CchScratch& sc, const CchRouteOut& o, hipStream_t s) {
-  static const bool serial_only = [] {
-    const char* v = std::getenv("ROUTEST_CCH_UNPACK");
-    return v && std::string(v) == "serial";
-  }();
+  const bool serial_only = unpack_serial();
   const int32_t* sub_up = m ? m->sub_up : nullptr;
   const int32_t* sub_dn = m ? m->sub_dn : nullptr;
   if (!serial_only) {

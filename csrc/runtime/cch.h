@@ -687,7 +687,9 @@ inline bool unpack_arc(const Topology& T, const Metric& m, int64_t a, int dir, s
 struct P2P {
   float sec = INF;
   float metres = INF;
-  int status = 1;                 // 0 found, 1 unreachable, 4 path longer than max_path
+  // 0 found, 1 unreachable, 4 path longer than max_path: the route exists, sec / metres are its
+  // own and only the path is withheld (the GPU kernels and both bindings report it that way)
+  int status = 1;
   std::vector<int32_t> path;      // node ids, s .. t
 };
 

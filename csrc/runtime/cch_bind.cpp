@@ -106,7 +106,9 @@ class PyCCH {
     return pm;
   }
 
-  // (sec f32[Q], metres f32[Q], status i32[Q], paths: list of int32 arrays or None)
+  // (sec f32[Q], metres f32[Q], status i32[Q], paths: list of int32 arrays or None).  Seconds and
+  // metres are the route's whenever it exists (status 0, and 4: only its listing was refused), -1
+  // for status 1 — what the GPU kernels report (csrc/cch_query.hip meet_kernel).
   py::tuple query(const PyMetric& pm, arr<int32_t> src, arr<int32_t> dst, bool want_path, int64_t max_path) {
     const py::ssize_t Q = src.shape(0);
     if (dst.shape(0) != Q) throw std::invalid_argument("src/dst length");
@@ -131,8 +133,8 @@ class PyCCH {
     py::array_t<int32_t> st(Q);
     py::list paths;
     for (py::ssize_t i = 0; i < Q; ++i) {
-      sec.mutable_data()[i] = res[i].status == 0 ? res[i].sec : -1.f;
-      met.mutable_data()[i] = res[i].status == 0 ? res[i].metres : -1.f;
+      sec.mutable_data()[i] = res[i].status != 1 ? res[i].sec : -1.f;
+      met.mutable_data()[i] = res[i].status != 1 ? res[i].metres : -1.f;
       st.mutable_data()[i] = res[i].status;
       if (want_path) paths.append(to_np(res[i].path));
     }

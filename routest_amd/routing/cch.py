@@ -232,7 +232,10 @@ class RoadRouter:
     # ---- queries ----
     def route(self, src: Sequence[int], dst: Sequence[int], ctx_or_key, want_path: bool = True):
         """(sec [Q], metres [Q], status [Q], paths: list of node-id arrays) — status 0 found,
-        1 unreachable, 4 longer than max_path."""
+        1 unreachable, 4 longer than max_path.  Seconds and metres are the route's whenever one
+        exists (status 0 and 4: a status-4 route is real, only its node listing was refused, so the
+        two do not depend on ``want_path``) and -1 for status 1; the path of a status-4 row is
+        empty.  The GPU and the CPU router agree on all of it bit for bit."""
         with self.pinned(ctx_or_key) as key:
             return self._route(src, dst, key, want_path)
 
