@@ -471,6 +471,39 @@ std::vector<torch::Tensor> route_greedy_cvrp(torch::Tensor D, torch::Tensor npts
   return {visit, trip_of, ntrips, status};
 }
 
+// K6b on K6's own outputs: visit is rewritten in place for rows with flag != 0 and status == 0.
+// Returns (moves i32 [R], trips_changed i32 [R], len_before_q i64 [R], len_after_q i64 [R]).
+std::vector<torch::Tensor> route_improve_trips(torch::Tensor D, torch::Tensor npts, torch::Tensor maxd,
+                                               torch::Tensor visit, torch::Tensor trip_of,
+                                               torch::Tensor status, torch::Tensor flag) {
+  for (auto* t : {&D, &npts, &maxd, &visit, &trip_of, &status, &flag}) check_dev(*t, "route tensor");
+  TORCH_CHECK(D.scalar_type() == torch::kFloat64 && D.dim() == 3 && D.size(1) == D.size(2),
+              "D must be f64 [R,NM,NM]");
+  const int R = (int)D.size(0), NM = (int)D.size(1);
+  TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
+  TORCH_CHECK(npts.scalar_type() == torch::kInt32 && npts.numel() == R, "npts must be i32 [R]");
+  TORCH_CHECK(maxd.scalar_type() == torch::kFloat64 && maxd.numel() == R, "maxd must be f64 [R]");
+  TORCH_CHECK(visit.scalar_type() == torch::kInt32 && visit.numel() == (int64_t)R * NM,
+              "visit must be i32 [R,NM]");
+  TORCH_CHECK(trip_of.scalar_type() == torch::kInt32 && trip_of.numel() == (int64_t)R * NM,
+              "trip_of must be i32 [R,NM]");
+  TORCH_CHECK(status.scalar_type() == torch::kInt32 && status.numel() == R, "status must be i32 [R]");
+  TORCH_CHECK(flag.scalar_type() == torch::kUInt8 && flag.numel() == R, "flag must be u8 [R]");
+  const c10::DeviceGuard guard(D.device());
+  auto iopt = D.options().dtype(torch::kInt32);
+  auto lopt = D.options().dtype(torch::kInt64);
+  auto moves = torch::empty({R}, iopt);
+  auto changed = torch::empty({R}, iopt);
+  auto before = torch::empty({R}, lopt);
+  auto after = torch::empty({R}, lopt);
+  RT_CHECK_HIP(rt::launch_improve_trips(
+      D.data_ptr<double>(), npts.data_ptr<int>(), maxd.data_ptr<double>(), flag.data_ptr<uint8_t>(),
+      status.data_ptr<int>(), R, NM, visit.data_ptr<int>(), trip_of.data_ptr<int>(),
+      moves.data_ptr<int>(), changed.data_ptr<int>(), (long long*)before.data_ptr<int64_t>(),
+      (long long*)after.data_ptr<int64_t>(), cur_stream(D)));
+  return {moves, changed, before, after};
+}
+
 rt::NormParams norm_from(const std::vector<double>& norm) {
   TORCH_CHECK(norm.size() == 8, "norm must hold 4 scales + 4 shifts");
   rt::NormParams np;
@@ -1412,6 +1445,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("eta_mlp3_blob16_bytes", [](int64_t H) { return (int64_t)rt::eta_mlp3_blob16_bytes((int)H); });
   m.def("route_haversine_matrix", &route_haversine_matrix, "K5: batched haversine matrices (f64)");
   m.def("route_greedy_cvrp", &route_greedy_cvrp, "K6: batched greedy multi-trip CVRP");
+  m.def("route_improve_trips", &route_improve_trips,
+        "K6b: intra-trip 2-opt / Or-opt on K6's outputs (visit rewritten in place)");
   m.def("big_layer1", &big_layer1, "wide MLP: featurize + layer 1 -> h1 (hperm order)",
         py::arg("records"), py::arg("w1p"), py::arg("H"), py::arg("norm"), py::arg("h1"),
         py::arg("xf") = py::none(), py::arg("mbits") = py::none());

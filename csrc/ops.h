@@ -221,6 +221,15 @@ hipError_t launch_greedy_cvrp(const double* D, const int* npts, const double* de
                               const double* cap, const double* maxd, int R, int NM, int* visit,
                               int* trip_of, int* ntrips, int* status, hipStream_t stream);
 
+// ---- K6b intra-trip 2-opt / Or-opt on K6's outputs : route_improve.hip ----
+// visit is rewritten in place for rows with flag != 0 and status == 0; the four statistics are
+// written for every row (0 for rows left alone).
+hipError_t launch_improve_trips(const double* D, const int* npts, const double* maxd,
+                                const unsigned char* flag, const int* status, int R, int NM,
+                                int* visit, const int* trip_of, int* moves, int* trips_changed,
+                                long long* len_before_q, long long* len_after_q,
+                                hipStream_t stream);
+
 // ---- persistent single-request scorer : persistent_serve.hip ----
 struct PersistentScorer;
 PersistentScorer* pscore_create(int device, const void* blob, int H, const NormParams& np, int cap,

@@ -106,4 +106,19 @@ struct HostBuf {
   }
 };
 
+// Trip improvement (K6b, route_improve.hip) over the trip buffers' rows: the per-row flag going up,
+// the four per-row statistics coming back with the trips.
+struct ImproveBufs {
+  HostBuf<unsigned char> h_flag;
+  DevBuf<unsigned char> d_flag;
+  HostBuf<int> h_moves, h_changed;
+  DevBuf<int> d_moves, d_changed;
+  HostBuf<long long> h_before, h_after;
+  DevBuf<long long> d_before, d_after;
+  bool reserve(size_t R) {
+    return !(h_flag.need(R) || d_flag.need(R) || h_moves.need(R) || h_changed.need(R) || d_moves.need(R) ||
+             d_changed.need(R) || h_before.need(R) || h_after.need(R) || d_before.need(R) || d_after.need(R));
+  }
+};
+
 }  // namespace rt

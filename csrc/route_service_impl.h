@@ -73,8 +73,10 @@ struct TripBufs {
   HostBuf<int> h_pts, h_npts2, h_rowg;
   DevBuf<int> d_pts, d_npts2, d_rowg;
   DevBuf<float> d_msec, d_mmet;
+  ImproveBufs imp;
   bool reserve(size_t R, size_t NM, bool road) {
     const size_t RN = R * NM;
+    if (!imp.reserve(R)) return false;
     if (road)
       return !(h_pts.need(RN) || h_npts2.need(R) || h_dem.need(RN) || h_cap.need(R) || h_maxd.need(R) ||
                h_visit.need(RN) || h_trip.need(RN) || h_ntrips.need(R) || h_status.need(R) || h_row0.need(RN) ||
@@ -291,7 +293,8 @@ struct RouteService::Impl {
   bool cch_groups(Batch& b);
   bool plan_multi(std::vector<RouteJob*>& jobs);
   bool plan_multi_road(Batch& b);
-  void unpack_plan(RouteJob* j, int n, int NM, int k);
+  hipError_t improve_rows(bool any, const int* d_npts, int R, int NM);
+  void unpack_plan(RouteJob* j, int n, int NM, int k, bool improved);
   // route_service_legs.hip
   std::vector<RouteJob*> snap_jobs(Batch& b);
   bool compact_out(Batch& b, int Q, bool edges, const char* what);

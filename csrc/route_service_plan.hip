@@ -1,6 +1,8 @@
 // Native route service, trip planning: the flush's routing contexts (CCH) and its multi-stop
 // requests' trips — ONE K5 + ONE K6 launch over coordinates, or the CCH's road matrices + K6
-// (see route_service.hip for the service, route_service_impl.h for its state).
+// (see route_service.hip for the service, route_service_impl.h for its state).  When a request of
+// the flush asks for "improve", K6b (route_improve.hip) re-sequences the asking rows' trips right
+// after K6, on the same buffers; a flush nobody asks in launches nothing more.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -198,7 +200,9 @@ bool RouteService::Impl::plan_multi(std::vector<RouteJob*>& jobs) {
     tb.h_npts.h[k] = n;
     tb.h_cap.h[k] = r.cap;
     tb.h_maxd.h[k] = r.maxd;
+    tb.imp.h_flag.h[k] = r.improve ? 1 : 0;
   }
+  const bool any_imp = std::any_of(m.begin(), m.end(), [](const RouteJob* j) { return j->req.improve; });
   hipError_t e = hipSuccess;
   cp(e, tb.d_lat.d, tb.h_lat.h, RN * 8);
   cp(e, tb.d_lon.d, tb.h_lon.h, RN * 8);
@@ -210,6 +214,7 @@ bool RouteService::Impl::plan_multi(std::vector<RouteJob*>& jobs) {
   if (e == hipSuccess)
     e = launch_greedy_cvrp(tb.d_D.d, tb.d_npts.d, tb.d_dem.d, tb.d_cap.d, tb.d_maxd.d, R, NM, tb.d_visit.d, tb.d_trip.d, tb.d_ntrips.d,
                            tb.d_status.d, stream);
+  if (e == hipSuccess) e = improve_rows(any_imp, tb.d_npts.d, R, NM);
   cp(e, tb.h_visit.h, tb.d_visit.d, RN * 4);
   cp(e, tb.h_trip.h, tb.d_trip.d, RN * 4);
   cp(e, tb.h_ntrips.h, tb.d_ntrips.d, (size_t)R * 4);
@@ -219,7 +224,7 @@ bool RouteService::Impl::plan_multi(std::vector<RouteJob*>& jobs) {
     e = qcopy2d(tb.h_row0.h, (size_t)NM * 8, tb.d_D.d, (size_t)NM * NM * 8, (size_t)NM * 8, (size_t)R, stream);
   if (e == hipSuccess) e = sync(stream, ev_gpu, "k5k6-matrix");
   if (e != hipSuccess) return false;
-  for (int k = 0; k < R; ++k) unpack_plan(m[k], tb.h_npts.h[k], NM, k);
+  for (int k = 0; k < R; ++k) unpack_plan(m[k], tb.h_npts.h[k], NM, k, any_imp);
   return true;
 }
 
@@ -273,8 +278,10 @@ bool RouteService::Impl::plan_multi_road(Batch& b) {
       tb.h_npts2.h[k] = n;
       tb.h_cap.h[k] = r.cap;
       tb.h_maxd.h[k] = r.maxd;
+      tb.imp.h_flag.h[k] = r.improve ? 1 : 0;
     }
   });
+  const bool any_imp = std::any_of(m.begin(), m.end(), [](const RouteJob* j) { return j->req.improve; });
   hipError_t e = hipSuccess;
   cp(e, tb.d_pts.d, tb.h_pts.h, RN * 4);
   cp(e, tb.d_npts2.d, tb.h_npts2.h, (size_t)R * 4);
@@ -289,6 +296,7 @@ bool RouteService::Impl::plan_multi_road(Batch& b) {
   if (e == hipSuccess)
     e = launch_greedy_cvrp(tb.d_D.d, tb.d_npts2.d, tb.d_dem.d, tb.d_cap.d, tb.d_maxd.d, R, NM, tb.d_visit.d, tb.d_trip.d, tb.d_ntrips.d,
                            tb.d_status.d, stream);
+  if (e == hipSuccess) e = improve_rows(any_imp, tb.d_npts2.d, R, NM);
   cp(e, tb.h_visit.h, tb.d_visit.d, RN * 4);
   cp(e, tb.h_trip.h, tb.d_trip.d, RN * 4);
   cp(e, tb.h_ntrips.h, tb.d_ntrips.d, (size_t)R * 4);
@@ -297,12 +305,29 @@ bool RouteService::Impl::plan_multi_road(Batch& b) {
     e = qcopy2d(tb.h_row0.h, (size_t)NM * 8, tb.d_D.d, (size_t)NM * NM * 8, (size_t)NM * 8, (size_t)R, stream);
   if (e == hipSuccess) e = sync(stream, ev_gpu, "cch-matrix+greedy");
   if (e != hipSuccess) return false;
-  for (int k = 0; k < R; ++k) unpack_plan(m[k], tb.h_npts2.h[k], NM, k);
+  for (int k = 0; k < R; ++k) unpack_plan(m[k], tb.h_npts2.h[k], NM, k, any_imp);
   return true;
 }
 
-// K6 output of request k -> its Plan (trips, or the infeasible stops by depot distance)
-void RouteService::Impl::unpack_plan(RouteJob* j, int n, int NM, int k) {
+// K6b over the rows K6 just wrote (same stream, before the read-back): the flags go up, visit is
+// rewritten in place for the asking rows, the statistics come back with the trips.
+hipError_t RouteService::Impl::improve_rows(bool any, const int* d_npts, int R, int NM) {
+  if (!any) return hipSuccess;
+  hipError_t e = hipSuccess;
+  cp(e, tb.imp.d_flag.d, tb.imp.h_flag.h, (size_t)R);
+  if (e == hipSuccess)
+    e = launch_improve_trips(tb.d_D.d, d_npts, tb.d_maxd.d, tb.imp.d_flag.d, tb.d_status.d, R, NM, tb.d_visit.d, tb.d_trip.d,
+                             tb.imp.d_moves.d, tb.imp.d_changed.d, tb.imp.d_before.d, tb.imp.d_after.d, stream);
+  cp(e, tb.imp.h_moves.h, tb.imp.d_moves.d, (size_t)R * 4);
+  cp(e, tb.imp.h_changed.h, tb.imp.d_changed.d, (size_t)R * 4);
+  cp(e, tb.imp.h_before.h, tb.imp.d_before.d, (size_t)R * 8);
+  cp(e, tb.imp.h_after.h, tb.imp.d_after.d, (size_t)R * 8);
+  return e;
+}
+
+// K6 output of request k -> its Plan (trips, or the infeasible stops by depot distance); `improved`:
+// K6b ran over the flush's rows, so an asking request carries its statistics
+void RouteService::Impl::unpack_plan(RouteJob* j, int n, int NM, int k, bool improved) {
   rtr::Plan& p = j->plan;
   const int* vis = tb.h_visit.h + (size_t)k * NM;
   const int* tof = tb.h_trip.h + (size_t)k * NM;
@@ -321,6 +346,13 @@ void RouteService::Impl::unpack_plan(RouteJob* j, int n, int NM, int k) {
   p.trips.assign(tb.h_ntrips.h[k], std::vector<int>{0});
   for (int i = 0; i < NM && vis[i] >= 0; ++i) p.trips[tof[i]].push_back(vis[i]);
   for (auto& t : p.trips) t.push_back(0);
+  if (improved && j->req.improve) {
+    p.improved = true;
+    p.imp.moves = tb.imp.h_moves.h[k];
+    p.imp.trips_changed = tb.imp.h_changed.h[k];
+    p.imp.len_before_q = tb.imp.h_before.h[k];
+    p.imp.len_after_q = tb.imp.h_after.h[k];
+  }
 }
 
 }  // namespace rt

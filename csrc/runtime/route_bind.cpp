@@ -6,7 +6,8 @@
 //  * route_optimize_cpu: the whole haversine-provider request on the CPU in C++ (parse, matrix,
 //    R21 greedy, directions, assembly) -> (status, body) or None (fallback to Python) — the CPU
 //    reference the GPU service is tested against, and a fast path for GPU-less deployments.
-//  * route_assemble_graph: graph-provider assembly from given trips + searched legs (tests).
+//  * route_assemble_graph: graph-provider assembly from given trips + searched legs (tests);
+//    `improvement`: the statistics of trips that were improved (routing/improve.py).
 //  * RouteStore / RowId: the route service's SQLite writer (route_store.h) over requests assembled
 //    by the two functions above (as_row=True) — its CPU tests.
 #include <pybind11/numpy.h>
@@ -257,6 +258,10 @@ bool optimize_cpu(PyRouteRow& o, bool json_ok, const std::string& engine, double
       for (int j = 0; j < n1; ++j)
         D[(size_t)i * n1 + j] = i == j ? 0.0 : rtr::haversine_m(lat[i], lon[i], lat[j], lon[j]) * circuity;
     plan.infeasible = !rtr::greedy_trips(D, n1, dem, r.cap, r.maxd, plan.trips, plan.infeasible_stops);
+    if (r.improve && !plan.infeasible) {
+      plan.imp = rtr::improve_trips(D, n1, r.maxd, plan.trips);
+      plan.improved = true;
+    }
   }
   std::vector<std::vector<std::pair<double, double>>> calls;
   rtr::directions_calls(r, plan, calls);
@@ -285,7 +290,7 @@ py::object route_assemble_graph(py::bytes body, const std::string& engine,
                                 py::array_t<double, py::array::c_style | py::array::forcecast> glon,
                                 py::array_t<int32_t, py::array::c_style | py::array::forcecast> nodes_of_calls,
                                 py::object trips_obj, py::dict legs_obj, py::object steps_obj, py::object cost_obj,
-                                bool with_record, bool as_row) {
+                                bool with_record, bool as_row, py::object improvement) {
   auto o = std::make_unique<PyRouteRow>();
   o->body = body;
   const std::string& b = o->body;
@@ -296,6 +301,14 @@ py::object route_assemble_graph(py::bytes body, const std::string& engine,
   o->row.root = &root;
   rtr::Plan plan;
   if (!trips_obj.is_none()) plan.trips = trips_obj.cast<std::vector<std::vector<int>>>();
+  if (!improvement.is_none()) {  // the given trips were improved: (moves, trips_changed, before_q, after_q)
+    const auto st = improvement.cast<std::tuple<long long, long long, long long, long long>>();
+    plan.imp.moves = std::get<0>(st);
+    plan.imp.trips_changed = std::get<1>(st);
+    plan.imp.len_before_q = std::get<2>(st);
+    plan.imp.len_after_q = std::get<3>(st);
+    plan.improved = true;
+  }
   std::vector<std::vector<std::pair<double, double>>> calls;
   rtr::directions_calls(r, plan, calls);
   // legs table
@@ -446,7 +459,8 @@ void bind_route(py::module& m) {
         py::arg("is_request_route") = false, py::arg("compat200") = true, py::arg("as_row") = false);
   m.def("route_assemble_graph", &route_assemble_graph, py::arg("body"), py::arg("engine"), py::arg("glat"),
         py::arg("glon"), py::arg("nodes"), py::arg("trips"), py::arg("legs"), py::arg("steps") = py::none(),
-        py::arg("cost") = py::none(), py::arg("with_record") = false, py::arg("as_row") = false);
+        py::arg("cost") = py::none(), py::arg("with_record") = false, py::arg("as_row") = false,
+        py::arg("improvement") = py::none());
   py::class_<PyRouteRow>(m, "RouteRow");
   py::class_<PyRouteStore>(m, "RouteStore")
       .def(py::init<const std::string&>(), py::arg("path"))

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "rt_core.h"
+#include "route_core.h"
 #include "http_client.h"
 
 namespace py = pybind11;
@@ -405,6 +406,27 @@ py::dict py_http_load_mixed(int port, int connections, double seconds, const std
   return d;
 }
 
+// ------------------------------------------------------------------ trip improvement (improve.py)
+// (D [n1, n1], trips, max_dist) -> (trips, {moves, trips_changed, len_before_q, len_after_q})
+py::tuple improve_trips(py::array_t<double, py::array::c_style | py::array::forcecast> D,
+                        std::vector<std::vector<int>> trips, double maxd) {
+  if (D.ndim() != 2 || D.shape(0) != D.shape(1)) throw std::invalid_argument("D must be square");
+  const int n1 = (int)D.shape(0);
+  for (const auto& t : trips) {
+    if (t.size() < 2) throw std::invalid_argument("a trip holds at least its two depot ends");
+    for (int v : t)
+      if (v < 0 || v >= n1) throw std::invalid_argument("trip index outside the matrix");
+  }
+  const std::vector<double> d(D.data(), D.data() + (size_t)n1 * n1);
+  const rtr::ImproveStats st = rtr::improve_trips(d, n1, maxd, trips);
+  py::dict s;
+  s["moves"] = st.moves;
+  s["trips_changed"] = st.trips_changed;
+  s["len_before_q"] = st.len_before_q;
+  s["len_after_q"] = st.len_after_q;
+  return py::make_tuple(trips, s);
+}
+
 PYBIND11_MODULE(_rt, m) {
   m.doc() = "routest_amd CPU native runtime";
   bind_route(m);
@@ -424,6 +446,7 @@ PYBIND11_MODULE(_rt, m) {
   m.def("iso_add_minutes", &iso_add_minutes);
   m.def("py_float_repr", &py_float_repr);
   m.def("greedy_trips", &greedy_trips);
+  m.def("improve_trips", &improve_trips, py::arg("D"), py::arg("trips"), py::arg("max_dist"));
   m.def("astar_batch", &astar_batch, py::arg("indptr"), py::arg("indices"), py::arg("cost"),
         py::arg("lat"), py::arg("lon"), py::arg("src"), py::arg("dst"), py::arg("inv_vmax"),
         py::arg("threads") = 8);

@@ -249,6 +249,48 @@ static void fuzz_route(std::mt19937_64& rng, int iters) {
   }
 }
 
+// route_core.h improve_trips: on random matrices (asymmetric, with NaN / inf / negative entries)
+// over the greedy's own trips every trip keeps its stops and ends, the quantized length never
+// grows, the statistics add up, and a second pass finds nothing more unless the first reverted
+static void fuzz_improve(std::mt19937_64& rng, int iters) {
+  for (int it = 0; it < iters / 100; ++it) {
+    const int n1 = 2 + (int)(rng() % 40);
+    std::vector<double> d((size_t)n1 * n1, 0.0), dem(n1, 1.0);
+    for (int a = 0; a < n1; ++a)
+      for (int b = 0; b < n1; ++b)
+        if (a != b) d[(size_t)a * n1 + b] = 100.0 + (double)(rng() % 1000000) / 37.0;
+    if (rng() % 4 == 0 && n1 > 3) {
+      d[(size_t)1 * n1 + 2] = NAN;
+      d[(size_t)2 * n1 + 3] = INFINITY;
+      d[(size_t)3 * n1 + 1] = -5.0;
+    }
+    const double cap = 1.0 + (double)(rng() % 50);
+    std::vector<std::vector<int>> trips, before;
+    std::vector<int> inf;
+    if (!rtr::greedy_trips(d, n1, dem, cap, 9e12, trips, inf)) continue;
+    before = trips;
+    const double maxd = rng() % 3 == 0 ? 1500.0 * n1 : 9e12;
+    const rtr::ImproveStats st = rtr::improve_trips(d, n1, maxd, trips);
+    CHECK(trips.size() == before.size(), "improve_trips changed the trip count");
+    long long changed = 0;
+    for (size_t t = 0; t < trips.size() && t < before.size(); ++t) {
+      std::vector<int> a = trips[t], b = before[t];
+      CHECK(a.size() == b.size() && a.front() == 0 && a.back() == 0, "improve_trips broke a trip's ends");
+      changed += a != b;
+      std::sort(a.begin(), a.end());
+      std::sort(b.begin(), b.end());
+      CHECK(a == b, "improve_trips changed a trip's stops");
+    }
+    CHECK(changed == st.trips_changed && st.len_after_q <= st.len_before_q && (st.moves > 0) == (changed > 0),
+          "improve_trips statistics: %lld changed vs %lld, %lld -> %lld", changed, st.trips_changed, st.len_before_q,
+          st.len_after_q);
+    const rtr::ImproveStats again = rtr::improve_trips(d, n1, 9e12, trips);
+    CHECK(again.len_before_q == st.len_after_q, "improve_trips: length after %lld, measured again %lld",
+          st.len_after_q, again.len_before_q);
+    if (maxd == 9e12) CHECK(again.moves == 0, "improve_trips left %lld moves", again.moves);
+  }
+}
+
 // alternatives.h: via nodes stay in range, unique, within the detour band, and reproducible; the
 // argmin treats non-finite scores as +inf
 static void fuzz_alternatives(std::mt19937_64& rng, int iters) {
@@ -530,6 +572,7 @@ int main(int argc, char** argv) {
   fuzz_float(rng, iters);
   fuzz_route(rng, iters);
   fuzz_coord_cache(rng, iters);
+  fuzz_improve(rng, iters);
   fuzz_alternatives(rng, iters);
   fuzz_history(rng, iters);
   store_while_reading();

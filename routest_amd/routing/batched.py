@@ -4,7 +4,10 @@
 tensors, then on a GPU runs ONE K5 launch (all haversine matrices) and ONE K6 launch (all greedy
 trip constructions, a wavefront per request); on CPU it runs the numpy/Python reference.  The
 result per request is the trips list (index lists into ``[source]+destinations``) or an
-:class:`InfeasibleStops` instance.  Sharding over several GPUs is done by
+:class:`InfeasibleStops` instance.  With per-request ``improve`` flags the flagged requests' trips
+are re-sequenced by the intra-trip 2-opt / Or-opt of :mod:`routing.improve` (on a GPU one more
+launch, K6b, on K6's own tensors) and the call returns ``(results, stats)``, ``stats[k]`` being the
+request's improvement statistics or ``None``.  Sharding over several GPUs is done by
 :class:`routing.route_batcher.RouteBatcher` (one worker thread per device, no collective).
 """
 from __future__ import annotations
@@ -16,6 +19,7 @@ import torch
 
 from ..ops import _ext
 from .greedy import InfeasibleStops, greedy_trips
+from .improve import improve_trips
 from .providers import haversine_matrix
 
 TripsOrError = Union[List[List[int]], InfeasibleStops]
@@ -71,8 +75,17 @@ def _unpack(visit: np.ndarray, trip_of: np.ndarray, ntrips: np.ndarray, status: 
     return out
 
 
+def _flags(improve: Optional[Sequence[Any]], R: int) -> Optional[np.ndarray]:
+    if improve is None:
+        return None
+    f = np.array([1 if v else 0 for v in improve], dtype=np.uint8)
+    if f.shape != (R,):
+        raise ValueError(f"improve must hold one flag per request ({R}), got {f.shape[0]}")
+    return f
+
+
 def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device,
-                         D: Optional[np.ndarray] = None) -> List[TripsOrError]:
+                         D: Optional[np.ndarray] = None, improve: Optional[Sequence[Any]] = None):
     # K6 indexes its LDS order / visited arrays by stop number: a request longer than the padded
     # width would write past them, so it is refused here, before anything reaches the device
     nm = int(D.shape[1]) if D is not None else int(np.shape(lat)[1])
@@ -87,32 +100,53 @@ def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device
         D = C.route_haversine_matrix(t(lat), t(lon), t(npts, torch.int32), float(circuity))
     else:
         D = t(np.ascontiguousarray(D, dtype=np.float64))
-    visit, trip_of, ntrips, status = C.route_greedy_cvrp(D, t(npts, torch.int32), t(dem), t(cap),
-                                                         t(maxd))
-    return _unpack(visit.cpu().numpy(), trip_of.cpu().numpy(), ntrips.cpu().numpy(),
-                   status.cpu().numpy(), npts, D.cpu().numpy())
+    flags = _flags(improve, len(n))
+    npts_t, maxd_t = t(npts, torch.int32), t(maxd)
+    visit, trip_of, ntrips, status = C.route_greedy_cvrp(D, npts_t, t(dem), t(cap), maxd_t)
+    stats = None
+    if flags is not None and flags.any():
+        # K6b rewrites visit in place for the flagged rows; a batch nobody flags launches nothing
+        stats = C.route_improve_trips(D, npts_t, maxd_t, visit, trip_of, status,
+                                      t(flags, torch.uint8))
+    status_h = status.cpu().numpy()
+    out = _unpack(visit.cpu().numpy(), trip_of.cpu().numpy(), ntrips.cpu().numpy(), status_h,
+                  npts, D.cpu().numpy())
+    if flags is None:
+        return out
+    cols = [c.cpu().numpy() for c in stats] if stats is not None else None
+    return out, [{"moves": int(cols[0][k]), "trips_changed": int(cols[1][k]),
+                  "len_before_q": int(cols[2][k]), "len_after_q": int(cols[3][k])}
+                 if flags[k] and status_h[k] == 0 else None for k in range(len(n))]
 
 
 def batched_trips_cpu(lat, lon, dem, npts, cap, maxd, circuity: float,
-                      D: Optional[np.ndarray] = None) -> List[TripsOrError]:
+                      D: Optional[np.ndarray] = None, improve: Optional[Sequence[Any]] = None):
     out: List[TripsOrError] = []
+    flags = _flags(improve, len(npts))
+    stats: List[Optional[Dict[str, int]]] = []
     for k in range(len(npts)):
         n = int(npts[k])
         d = D[k, :n, :n] if D is not None else haversine_matrix(lat[k, :n], lon[k, :n], circuity)
+        st = None
         try:
-            out.append(greedy_trips(d.tolist(), dem[k, :n].tolist(), float(cap[k]), float(maxd[k])))
+            trips = greedy_trips(d.tolist(), dem[k, :n].tolist(), float(cap[k]), float(maxd[k]))
+            if flags is not None and flags[k]:
+                trips, st = improve_trips(d, trips, float(maxd[k]))
+            out.append(trips)
         except InfeasibleStops as e:
             out.append(e)
-    return out
+        stats.append(st)
+    return out if flags is None else (out, stats)
 
 
 def batched_trips(requests: Sequence[Dict[str, Any]], circuity: float = 1.3,
-                  device: Optional[Any] = None, D: Optional[np.ndarray] = None) -> List[TripsOrError]:
+                  device: Optional[Any] = None, D: Optional[np.ndarray] = None,
+                  improve: Optional[Sequence[Any]] = None):
     """``D``: given distance matrices [R, nm, nm] (road metres from the CCH router) instead of the
-    haversine K5."""
+    haversine K5.  ``improve``: one flag per request; when given, returns ``(results, stats)``."""
     if not requests:
-        return []
+        return [] if improve is None else ([], [])
     packed = pack_requests(requests)
     if device is not None and torch.device(device).type == "cuda":
-        return batched_trips_device(*packed, circuity=circuity, device=device, D=D)
-    return batched_trips_cpu(*packed, circuity=circuity, D=D)
+        return batched_trips_device(*packed, circuity=circuity, device=device, D=D, improve=improve)
+    return batched_trips_cpu(*packed, circuity=circuity, D=D, improve=improve)

@@ -13,6 +13,11 @@ Reference: ``optimize_route`` (``RO/Flaskr/utils.py:10-48``), ``_point_to_point`
 * metadata ``vehicle_type``, ``driver_name``, ``engine``.
 
 Fixed: infeasible stops return an error instead of hanging (Appendix B #3).
+
+Opt-in (``"improve": true`` on a multi-stop request, JSON ``true`` exactly): every trip of the
+greedy is re-sequenced by the intra-trip 2-opt / Or-opt of :mod:`routing.improve` before the legs
+are routed, and ``properties.improvement`` reports what it did.  Single-destination requests and
+``alternatives`` requests ignore the field; without it every response is unchanged.
 The batched GPU path for many concurrent requests (K5 + K6) is :func:`optimize_many`.
 """
 from __future__ import annotations
@@ -22,6 +27,7 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 
 from .greedy import InfeasibleStops, greedy_trips, optimized_order
+from .improve import improve_trips, improvement_properties, wants_improve
 from .providers import ProviderError, _bbox, profile_for
 
 
@@ -103,7 +109,10 @@ def assemble_trips(provider, all_points: List[Dict[str, Any]], trips: List[List[
 
 
 def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, Any],
-               trips: Optional[List[List[int]]] = None, ctx=None) -> Dict[str, Any]:
+               trips: Optional[List[List[int]]] = None, ctx=None, improve: bool = False,
+               improvement: Optional[Dict[str, int]] = None) -> Dict[str, Any]:
+    """``improve``: re-sequence the trips built here (routing/improve.py).  Trips given by the
+    caller are taken as they are; ``improvement`` holds their statistics if they were improved."""
     all_points = [source] + list(destinations)
     if trips is None:
         try:
@@ -114,17 +123,25 @@ def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, A
         max_dist = _float(driver.get("maximum_distance", 9e12), 9e12)
         demand = [0.0] + [_float(p.get("payload", 0), 0.0) for p in destinations]
         try:
-            trips = greedy_trips(np.asarray(d, dtype=np.float64).tolist(), demand, cap, max_dist)
+            dm = np.asarray(d, dtype=np.float64)
+            trips = greedy_trips(dm.tolist(), demand, cap, max_dist)
         except InfeasibleStops as e:
             return {"error": str(e)}
-    return assemble_trips(provider, all_points, trips, profile, source, destinations, ctx)
+        if improve:
+            trips, improvement = improve_trips(dm, trips, max_dist)
+    feature = assemble_trips(provider, all_points, trips, profile, source, destinations, ctx)
+    if improvement is not None and "error" not in feature:
+        feature["properties"]["improvement"] = improvement_properties(improvement)
+    return feature
 
 
 def optimize_route(input_data: Any, provider, engine: str = "backend:mi355x",
-                   trips: Optional[List[List[int]]] = None, ctx=None) -> Dict[str, Any]:
+                   trips: Optional[List[List[int]]] = None, ctx=None,
+                   improvement: Optional[Dict[str, int]] = None) -> Dict[str, Any]:
     """Pure function: GeoJSON Feature on success, ``{"error": ...}`` on failure (R19).  ``ctx``:
     the request's routing context as resolved when its legs were planned (the batcher), so a
-    request without ``pickup_time`` is assembled under the same week-hour it was routed in."""
+    request without ``pickup_time`` is assembled under the same week-hour it was routed in.
+    ``improvement``: the statistics of given ``trips`` that were already improved (the batcher)."""
     if not input_data or not isinstance(input_data, dict) or not input_data.get("destination_points"):
         return {"error": "no destination points specified."}
     driver = input_data.get("driver_details") or {}
@@ -150,7 +167,8 @@ def optimize_route(input_data: Any, provider, engine: str = "backend:mi355x",
         p["destinations"] = [destinations[0]]
         _annotate(feature, driver, vehicle_type, engine)
         return feature
-    feature = multi_stop(provider, source, destinations, profile, driver, trips, ctx)
+    feature = multi_stop(provider, source, destinations, profile, driver, trips, ctx,
+                         improve=wants_improve(input_data), improvement=improvement)
     if "error" in feature:
         return feature
     _annotate(feature, driver, vehicle_type, engine)
@@ -167,14 +185,17 @@ def optimize_many(requests: Sequence[Dict[str, Any]], provider, engine: str = "b
              if isinstance(r, dict) and isinstance(r.get("destination_points"), list)
              and len(r["destination_points"]) > 1 and isinstance(r.get("source_point"), dict)]
     trip_map: Dict[int, Any] = {}
+    stat_map: Dict[int, Any] = {}
     if multi and getattr(provider, "name", "") == "haversine":
-        res = batched_trips([requests[i] for i in multi], circuity=provider.circuity, device=device)
+        res, stats = batched_trips([requests[i] for i in multi], circuity=provider.circuity,
+                                   device=device, improve=[wants_improve(requests[i]) for i in multi])
         trip_map = dict(zip(multi, res))
+        stat_map = dict(zip(multi, stats))
     out = []
     for i, r in enumerate(requests):
         t = trip_map.get(i)
         if isinstance(t, InfeasibleStops):
             out.append({"error": str(t)})
             continue
-        out.append(optimize_route(r, provider, engine, trips=t))
+        out.append(optimize_route(r, provider, engine, trips=t, improvement=stat_map.get(i)))
     return out

@@ -38,6 +38,7 @@ from ..utils.metrics import REGISTRY
 from ..utils.queues import get_until
 from .batched import batched_trips
 from .greedy import InfeasibleStops
+from .improve import wants_improve
 from .optimizer import optimize_route
 from .providers import ProviderError
 
@@ -148,15 +149,17 @@ class RouteBatcher:
         request's road-metre matrix, ONE greedy launch (K6) over those matrices, then every trip leg
         (and point-to-point request) in ONE leg launch.  Each context group runs start to finish
         under a pin of its metric, and its edge costs are copied to the host then, so a flush with
-        more contexts than the metric cache holds never loses one in between.  Returns (trips by
-        request, legs dict, host edge costs by metric key)."""
+        more contexts than the metric cache holds never loses one in between.  Requests that ask
+        for ``improve`` get their trips re-sequenced right after K6 (K6b), before the legs.  Returns
+        (trips by request, legs dict, host edge costs by metric key, improvement stats by request)."""
         prov = self.provider
         trips: Dict[int, Any] = {}
+        stats: Dict[int, Any] = {}
         legs: Dict[tuple, tuple] = {}
         host_costs: Dict[int, np.ndarray] = {}
         valid = [k for k, r in enumerate(payloads) if _valid_points(r)]
         if not valid:
-            return trips, legs, host_costs
+            return trips, legs, host_costs, stats
         groups: Dict[Any, List[int]] = {}
         first: Dict[Any, Any] = {}
         for k in valid:
@@ -165,12 +168,12 @@ class RouteBatcher:
             first.setdefault(gk, ctxs[k])
         for gk, ks in groups.items():
             with prov.pinned_metric(first[gk], device) as key:
-                self._plan_group(payloads, ks, key, device, trips, legs)
+                self._plan_group(payloads, ks, key, device, trips, legs, stats)
                 if getattr(prov, "_steps", None) is not None:
                     host_costs[key] = prov.edge_seconds(key, device)
-        return trips, legs, host_costs
+        return trips, legs, host_costs, stats
 
-    def _plan_group(self, payloads, ks, key, device, trips, legs) -> None:
+    def _plan_group(self, payloads, ks, key, device, trips, legs, stats) -> None:
         prov = self.provider
         pts = {k: [payloads[k]["source_point"]] + list(payloads[k]["destination_points"]) for k in ks}
         flat = np.array([[p["lon"], p["lat"]] for k in ks for p in pts[k]], dtype=np.float64)
@@ -188,8 +191,10 @@ class RouteBatcher:
             for i, (k, (_, met)) in enumerate(zip(multi, mats)):
                 n = len(pts[k])
                 D[i, :n, :n] = met
-            res = batched_trips([payloads[k] for k in multi], device=device, D=D)
+            res, st = batched_trips([payloads[k] for k in multi], device=device, D=D,
+                                    improve=[wants_improve(payloads[k]) for k in multi])
             trips.update(zip(multi, res))
+            stats.update(zip(multi, st))
         pairs = set()
         for k in ks:
             if len(pts[k]) == 2:
@@ -241,38 +246,41 @@ class RouteBatcher:
         return {(key, s, t): r for (s, t), r in zip(pairs, res)}
 
     def plan_batch(self, payloads: Sequence[Any], device=None) -> List[tuple]:
-        """The GPU phases of a flush: per request ``(trips or InfeasibleStops or None, view, ctx)``."""
+        """The GPU phases of a flush: per request ``(trips or InfeasibleStops or None, view, ctx,
+        improvement stats or None)``."""
         payloads = list(payloads)
         name = getattr(self.provider, "name", "")
         trips: Dict[int, Any] = {}
+        stats: Dict[int, Any] = {}
         view = self.provider
         if name == "graph" and getattr(self.provider, "engine", "astar") != "astar":
             ctxs = self._contexts(payloads)
             try:
-                trips, legs, hc = self._graph_plan(payloads, device, ctxs)
+                trips, legs, hc, stats = self._graph_plan(payloads, device, ctxs)
             except ProviderError as e:
-                return [(e, None, None) for _ in payloads]
+                return [(e, None, None, None) for _ in payloads]
             view = _LegView(self.provider, legs, device, hc)
-            return [(trips.get(k), view, ctxs[k]) for k in range(len(payloads))]
+            return [(trips.get(k), view, ctxs[k], stats.get(k)) for k in range(len(payloads))]
         multi = [k for k, r in enumerate(payloads) if _valid_points(r) and len(r["destination_points"]) > 1]
         if multi and name in ("haversine", "graph"):
-            res = batched_trips([payloads[k] for k in multi], circuity=self.provider.circuity,
-                                device=device)
+            res, st = batched_trips([payloads[k] for k in multi], circuity=self.provider.circuity,
+                                    device=device, improve=[wants_improve(payloads[k]) for k in multi])
             trips = dict(zip(multi, res))
+            stats = dict(zip(multi, st))
         if name == "graph":
             try:
                 view = _LegView(self.provider, self._graph_legs(payloads, trips, device), device)
             except ProviderError as e:
-                return [(e, None, None) for _ in payloads]
-        return [(trips.get(k), view, None) for k in range(len(payloads))]
+                return [(e, None, None, None) for _ in payloads]
+        return [(trips.get(k), view, None, stats.get(k)) for k in range(len(payloads))]
 
     def assemble(self, payload: Any, plan: tuple) -> Dict[str, Any]:
         """Host side of one request: GeoJSON Feature (or error) from its planned trips/legs, under
         the routing context it was planned with."""
-        t, view, ctx = plan
+        t, view, ctx, improvement = plan
         if isinstance(t, (InfeasibleStops, ProviderError)):
             return {"error": str(t)}
-        return optimize_route(payload, view, self.engine, trips=t, ctx=ctx)
+        return optimize_route(payload, view, self.engine, trips=t, ctx=ctx, improvement=improvement)
 
     def run_batch(self, payloads: Sequence[Any], device=None) -> List[Dict[str, Any]]:
         """Optimise a list of request payloads together (plan + assembly; also callable directly,
