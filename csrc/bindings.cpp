@@ -504,6 +504,50 @@ std::vector<torch::Tensor> route_improve_trips(torch::Tensor D, torch::Tensor np
   return {moves, changed, before, after};
 }
 
+// K6c on K6's own outputs: visit / trip_of / ntrips are rewritten in place for rows with flag != 0
+// and status == 0.  Returns (moves, rejected, trips_before, trips_after i32 [R], len_before_q,
+// len_after_q i64 [R]).
+std::vector<torch::Tensor> route_exchange_trips(torch::Tensor D, torch::Tensor npts, torch::Tensor demand,
+                                                torch::Tensor cap, torch::Tensor maxd, torch::Tensor visit,
+                                                torch::Tensor trip_of, torch::Tensor ntrips, torch::Tensor status,
+                                                torch::Tensor flag, int64_t move_cap) {
+  for (auto* t : {&D, &npts, &demand, &cap, &maxd, &visit, &trip_of, &ntrips, &status, &flag})
+    check_dev(*t, "route tensor");
+  TORCH_CHECK(D.scalar_type() == torch::kFloat64 && D.dim() == 3 && D.size(1) == D.size(2),
+              "D must be f64 [R,NM,NM]");
+  const int R = (int)D.size(0), NM = (int)D.size(1);
+  TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
+  TORCH_CHECK(npts.scalar_type() == torch::kInt32 && npts.numel() == R, "npts must be i32 [R]");
+  TORCH_CHECK(demand.scalar_type() == torch::kFloat64 && demand.numel() == (int64_t)R * NM,
+              "demand must be f64 [R,NM]");
+  TORCH_CHECK(cap.scalar_type() == torch::kFloat64 && cap.numel() == R, "cap must be f64 [R]");
+  TORCH_CHECK(maxd.scalar_type() == torch::kFloat64 && maxd.numel() == R, "maxd must be f64 [R]");
+  TORCH_CHECK(visit.scalar_type() == torch::kInt32 && visit.numel() == (int64_t)R * NM,
+              "visit must be i32 [R,NM]");
+  TORCH_CHECK(trip_of.scalar_type() == torch::kInt32 && trip_of.numel() == (int64_t)R * NM,
+              "trip_of must be i32 [R,NM]");
+  TORCH_CHECK(ntrips.scalar_type() == torch::kInt32 && ntrips.numel() == R, "ntrips must be i32 [R]");
+  TORCH_CHECK(status.scalar_type() == torch::kInt32 && status.numel() == R, "status must be i32 [R]");
+  TORCH_CHECK(flag.scalar_type() == torch::kUInt8 && flag.numel() == R, "flag must be u8 [R]");
+  TORCH_CHECK(move_cap >= -1 && move_cap <= INT_MAX, "move_cap must be -1 (default) or a move count");
+  const c10::DeviceGuard guard(D.device());
+  auto iopt = D.options().dtype(torch::kInt32);
+  auto lopt = D.options().dtype(torch::kInt64);
+  auto moves = torch::empty({R}, iopt);
+  auto rejected = torch::empty({R}, iopt);
+  auto tbefore = torch::empty({R}, iopt);
+  auto tafter = torch::empty({R}, iopt);
+  auto before = torch::empty({R}, lopt);
+  auto after = torch::empty({R}, lopt);
+  RT_CHECK_HIP(rt::launch_exchange_trips(
+      D.data_ptr<double>(), npts.data_ptr<int>(), demand.data_ptr<double>(), cap.data_ptr<double>(),
+      maxd.data_ptr<double>(), flag.data_ptr<uint8_t>(), status.data_ptr<int>(), R, NM, (int)move_cap,
+      visit.data_ptr<int>(), trip_of.data_ptr<int>(), ntrips.data_ptr<int>(), moves.data_ptr<int>(),
+      rejected.data_ptr<int>(), tbefore.data_ptr<int>(), tafter.data_ptr<int>(),
+      (long long*)before.data_ptr<int64_t>(), (long long*)after.data_ptr<int64_t>(), cur_stream(D)));
+  return {moves, rejected, tbefore, tafter, before, after};
+}
+
 rt::NormParams norm_from(const std::vector<double>& norm) {
   TORCH_CHECK(norm.size() == 8, "norm must hold 4 scales + 4 shifts");
   rt::NormParams np;
@@ -1447,6 +1491,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("route_greedy_cvrp", &route_greedy_cvrp, "K6: batched greedy multi-trip CVRP");
   m.def("route_improve_trips", &route_improve_trips,
         "K6b: intra-trip 2-opt / Or-opt on K6's outputs (visit rewritten in place)");
+  m.def("route_exchange_trips", &route_exchange_trips,
+        "K6c: inter-trip relocate / swap on K6's outputs (visit, trip_of, ntrips rewritten in place)",
+        py::arg("D"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"), py::arg("visit"),
+        py::arg("trip_of"), py::arg("ntrips"), py::arg("status"), py::arg("flag"), py::arg("move_cap") = -1);
   m.def("big_layer1", &big_layer1, "wide MLP: featurize + layer 1 -> h1 (hperm order)",
         py::arg("records"), py::arg("w1p"), py::arg("H"), py::arg("norm"), py::arg("h1"),
         py::arg("xf") = py::none(), py::arg("mbits") = py::none());

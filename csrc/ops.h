@@ -230,6 +230,17 @@ hipError_t launch_improve_trips(const double* D, const int* npts, const double* 
                                 long long* len_before_q, long long* len_after_q,
                                 hipStream_t stream);
 
+// ---- K6c inter-trip relocate / swap on K6's outputs : route_exchange.hip ----
+// visit, trip_of and ntrips are rewritten in place for rows with flag != 0 and status == 0 (still
+// grouped by trip, trip indices compacted); the six statistics are written for every row (0 for
+// rows left alone).  move_cap < 0: the default, 4 moves per stop.
+hipError_t launch_exchange_trips(const double* D, const int* npts, const double* demand,
+                                 const double* cap, const double* maxd, const unsigned char* flag,
+                                 const int* status, int R, int NM, int move_cap, int* visit,
+                                 int* trip_of, int* ntrips, int* moves, int* rejected,
+                                 int* trips_before, int* trips_after, long long* len_before_q,
+                                 long long* len_after_q, hipStream_t stream);
+
 // ---- persistent single-request scorer : persistent_serve.hip ----
 struct PersistentScorer;
 PersistentScorer* pscore_create(int device, const void* blob, int H, const NormParams& np, int cap,

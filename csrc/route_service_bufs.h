@@ -115,9 +115,22 @@ struct ImproveBufs {
   DevBuf<int> d_moves, d_changed;
   HostBuf<long long> h_before, h_after;
   DevBuf<long long> d_before, d_after;
+  // Trip exchange (K6c, route_exchange.hip) between two K6b launches: its own flag, its statistics,
+  // and the second K6b launch's (which runs over the exchange rows only and so must not write the
+  // first launch's buffers, where the improve-only rows' statistics live).
+  HostBuf<unsigned char> h_xflag;
+  DevBuf<unsigned char> d_xflag;
+  HostBuf<int> h_xmoves, h_xtb, h_xta, h_moves2;
+  DevBuf<int> d_xmoves, d_xrej, d_xtb, d_xta, d_moves2, d_changed2;
+  HostBuf<long long> h_after2;
+  DevBuf<long long> d_xbefore, d_xafter, d_before2, d_after2;
   bool reserve(size_t R) {
     return !(h_flag.need(R) || d_flag.need(R) || h_moves.need(R) || h_changed.need(R) || d_moves.need(R) ||
-             d_changed.need(R) || h_before.need(R) || h_after.need(R) || d_before.need(R) || d_after.need(R));
+             d_changed.need(R) || h_before.need(R) || h_after.need(R) || d_before.need(R) || d_after.need(R) ||
+             h_xflag.need(R) || d_xflag.need(R) || h_xmoves.need(R) || h_xtb.need(R) || h_xta.need(R) ||
+             h_moves2.need(R) || d_xmoves.need(R) || d_xrej.need(R) || d_xtb.need(R) || d_xta.need(R) ||
+             d_moves2.need(R) || d_changed2.need(R) || h_after2.need(R) || d_xbefore.need(R) || d_xafter.need(R) ||
+             d_before2.need(R) || d_after2.need(R));
   }
 };
 

@@ -2,7 +2,8 @@
 // requests' trips — ONE K5 + ONE K6 launch over coordinates, or the CCH's road matrices + K6
 // (see route_service.hip for the service, route_service_impl.h for its state).  When a request of
 // the flush asks for "improve", K6b (route_improve.hip) re-sequences the asking rows' trips right
-// after K6, on the same buffers; a flush nobody asks in launches nothing more.
+// after K6, on the same buffers; for "exchange" K6c (route_exchange.hip) and a second K6b follow
+// over the asking rows.  A flush nobody asks in launches nothing more.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -200,9 +201,10 @@ bool RouteService::Impl::plan_multi(std::vector<RouteJob*>& jobs) {
     tb.h_npts.h[k] = n;
     tb.h_cap.h[k] = r.cap;
     tb.h_maxd.h[k] = r.maxd;
-    tb.imp.h_flag.h[k] = r.improve ? 1 : 0;
+    tb.imp.h_flag.h[k] = r.improve || r.exchange ? 1 : 0;
+    tb.imp.h_xflag.h[k] = r.exchange ? 1 : 0;
   }
-  const bool any_imp = std::any_of(m.begin(), m.end(), [](const RouteJob* j) { return j->req.improve; });
+  const bool any_imp = std::any_of(m.begin(), m.end(), [](const RouteJob* j) { return j->req.improve || j->req.exchange; });
   hipError_t e = hipSuccess;
   cp(e, tb.d_lat.d, tb.h_lat.h, RN * 8);
   cp(e, tb.d_lon.d, tb.h_lon.h, RN * 8);
@@ -278,10 +280,11 @@ bool RouteService::Impl::plan_multi_road(Batch& b) {
       tb.h_npts2.h[k] = n;
       tb.h_cap.h[k] = r.cap;
       tb.h_maxd.h[k] = r.maxd;
-      tb.imp.h_flag.h[k] = r.improve ? 1 : 0;
+      tb.imp.h_flag.h[k] = r.improve || r.exchange ? 1 : 0;
+    tb.imp.h_xflag.h[k] = r.exchange ? 1 : 0;
     }
   });
-  const bool any_imp = std::any_of(m.begin(), m.end(), [](const RouteJob* j) { return j->req.improve; });
+  const bool any_imp = std::any_of(m.begin(), m.end(), [](const RouteJob* j) { return j->req.improve || j->req.exchange; });
   hipError_t e = hipSuccess;
   cp(e, tb.d_pts.d, tb.h_pts.h, RN * 4);
   cp(e, tb.d_npts2.d, tb.h_npts2.h, (size_t)R * 4);
@@ -322,6 +325,23 @@ hipError_t RouteService::Impl::improve_rows(bool any, const int* d_npts, int R, 
   cp(e, tb.imp.h_changed.h, tb.imp.d_changed.d, (size_t)R * 4);
   cp(e, tb.imp.h_before.h, tb.imp.d_before.d, (size_t)R * 8);
   cp(e, tb.imp.h_after.h, tb.imp.d_after.d, (size_t)R * 8);
+  if (!std::any_of(tb.imp.h_xflag.h, tb.imp.h_xflag.h + R, [](unsigned char f) { return f != 0; })) return e;
+  // "exchange" rows: K6c (route_exchange.hip) moves stops between their trips, then K6b once more
+  // over those rows only, into second statistics buffers (K6b writes every row's statistics, and
+  // the improve-only rows' are in the first)
+  cp(e, tb.imp.d_xflag.d, tb.imp.h_xflag.h, (size_t)R);
+  if (e == hipSuccess)
+    e = launch_exchange_trips(tb.d_D.d, d_npts, tb.d_dem.d, tb.d_cap.d, tb.d_maxd.d, tb.imp.d_xflag.d, tb.d_status.d, R, NM, -1,
+                              tb.d_visit.d, tb.d_trip.d, tb.d_ntrips.d, tb.imp.d_xmoves.d, tb.imp.d_xrej.d, tb.imp.d_xtb.d,
+                              tb.imp.d_xta.d, tb.imp.d_xbefore.d, tb.imp.d_xafter.d, stream);
+  if (e == hipSuccess)
+    e = launch_improve_trips(tb.d_D.d, d_npts, tb.d_maxd.d, tb.imp.d_xflag.d, tb.d_status.d, R, NM, tb.d_visit.d, tb.d_trip.d,
+                             tb.imp.d_moves2.d, tb.imp.d_changed2.d, tb.imp.d_before2.d, tb.imp.d_after2.d, stream);
+  cp(e, tb.imp.h_xmoves.h, tb.imp.d_xmoves.d, (size_t)R * 4);
+  cp(e, tb.imp.h_xtb.h, tb.imp.d_xtb.d, (size_t)R * 4);
+  cp(e, tb.imp.h_xta.h, tb.imp.d_xta.d, (size_t)R * 4);
+  cp(e, tb.imp.h_moves2.h, tb.imp.d_moves2.d, (size_t)R * 4);
+  cp(e, tb.imp.h_after2.h, tb.imp.d_after2.d, (size_t)R * 8);
   return e;
 }
 
@@ -346,7 +366,16 @@ void RouteService::Impl::unpack_plan(RouteJob* j, int n, int NM, int k, bool imp
   p.trips.assign(tb.h_ntrips.h[k], std::vector<int>{0});
   for (int i = 0; i < NM && vis[i] >= 0; ++i) p.trips[tof[i]].push_back(vis[i]);
   for (auto& t : p.trips) t.push_back(0);
-  if (improved && j->req.improve) {
+  if (improved && j->req.exchange) {  // exchange.py compose_stats
+    p.improved = true;
+    p.imp.exchange = true;
+    p.imp.moves = (long long)tb.imp.h_moves.h[k] + tb.imp.h_moves2.h[k];
+    p.imp.exchange_moves = tb.imp.h_xmoves.h[k];
+    p.imp.trips_before = tb.imp.h_xtb.h[k];
+    p.imp.trips_after = tb.imp.h_xta.h[k];
+    p.imp.len_before_q = tb.imp.h_before.h[k];
+    p.imp.len_after_q = tb.imp.h_after2.h[k];
+  } else if (improved && j->req.improve) {
     p.improved = true;
     p.imp.moves = tb.imp.h_moves.h[k];
     p.imp.trips_changed = tb.imp.h_changed.h[k];

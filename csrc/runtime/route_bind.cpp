@@ -258,7 +258,10 @@ bool optimize_cpu(PyRouteRow& o, bool json_ok, const std::string& engine, double
       for (int j = 0; j < n1; ++j)
         D[(size_t)i * n1 + j] = i == j ? 0.0 : rtr::haversine_m(lat[i], lon[i], lat[j], lon[j]) * circuity;
     plan.infeasible = !rtr::greedy_trips(D, n1, dem, r.cap, r.maxd, plan.trips, plan.infeasible_stops);
-    if (r.improve && !plan.infeasible) {
+    if (r.exchange && !plan.infeasible) {
+      plan.imp = rtr::improve_exchange_trips(D, n1, dem, r.cap, r.maxd, plan.trips);
+      plan.improved = true;
+    } else if (r.improve && !plan.infeasible) {
       plan.imp = rtr::improve_trips(D, n1, r.maxd, plan.trips);
       plan.improved = true;
     }
@@ -301,7 +304,19 @@ py::object route_assemble_graph(py::bytes body, const std::string& engine,
   o->row.root = &root;
   rtr::Plan plan;
   if (!trips_obj.is_none()) plan.trips = trips_obj.cast<std::vector<std::vector<int>>>();
-  if (!improvement.is_none()) {  // the given trips were improved: (moves, trips_changed, before_q, after_q)
+  if (!improvement.is_none() && py::len(improvement) == 6) {
+    // the given trips went through the exchange pipeline:
+    // (moves, exchange_moves, trips_before, trips_after, before_q, after_q)
+    const auto st = improvement.cast<std::tuple<long long, long long, long long, long long, long long, long long>>();
+    plan.imp.exchange = true;
+    plan.imp.moves = std::get<0>(st);
+    plan.imp.exchange_moves = std::get<1>(st);
+    plan.imp.trips_before = std::get<2>(st);
+    plan.imp.trips_after = std::get<3>(st);
+    plan.imp.len_before_q = std::get<4>(st);
+    plan.imp.len_after_q = std::get<5>(st);
+    plan.improved = true;
+  } else if (!improvement.is_none()) {  // the given trips were improved: (moves, trips_changed, before_q, after_q)
     const auto st = improvement.cast<std::tuple<long long, long long, long long, long long>>();
     plan.imp.moves = std::get<0>(st);
     plan.imp.trips_changed = std::get<1>(st);

@@ -427,6 +427,37 @@ py::tuple improve_trips(py::array_t<double, py::array::c_style | py::array::forc
   return py::make_tuple(trips, s);
 }
 
+// ------------------------------------------------------------------ trip exchange (exchange.py)
+// (D [n1, n1], trips, demand [n1], cap, max_dist, move_cap) -> (trips, {moves, rejected,
+// trips_before, trips_after, len_before_q, len_after_q})
+py::tuple exchange_trips(py::array_t<double, py::array::c_style | py::array::forcecast> D,
+                         std::vector<std::vector<int>> trips, std::vector<double> demand, double cap, double maxd,
+                         py::object move_cap) {
+  if (D.ndim() != 2 || D.shape(0) != D.shape(1)) throw std::invalid_argument("D must be square");
+  const int n1 = (int)D.shape(0);
+  if ((int)demand.size() != n1) throw std::invalid_argument("demand holds one entry per point");
+  std::vector<char> seen(n1, 0);
+  for (const auto& t : trips) {
+    if (t.size() < 2 || t.front() != 0 || t.back() != 0)
+      throw std::invalid_argument("a trip starts and ends at the depot");
+    for (size_t p = 1; p + 1 < t.size(); ++p) {
+      if (t[p] < 1 || t[p] >= n1 || seen[t[p]]) throw std::invalid_argument("trips must hold every stop once");
+      seen[t[p]] = 1;
+    }
+  }
+  const std::vector<double> d(D.data(), D.data() + (size_t)n1 * n1);
+  const rtr::ExchangeStats st =
+      rtr::exchange_trips(d, n1, demand, cap, maxd, trips, move_cap.is_none() ? -1LL : move_cap.cast<long long>());
+  py::dict s;
+  s["moves"] = st.moves;
+  s["rejected"] = st.rejected;
+  s["trips_before"] = st.trips_before;
+  s["trips_after"] = st.trips_after;
+  s["len_before_q"] = st.len_before_q;
+  s["len_after_q"] = st.len_after_q;
+  return py::make_tuple(trips, s);
+}
+
 PYBIND11_MODULE(_rt, m) {
   m.doc() = "routest_amd CPU native runtime";
   bind_route(m);
@@ -447,6 +478,8 @@ PYBIND11_MODULE(_rt, m) {
   m.def("py_float_repr", &py_float_repr);
   m.def("greedy_trips", &greedy_trips);
   m.def("improve_trips", &improve_trips, py::arg("D"), py::arg("trips"), py::arg("max_dist"));
+  m.def("exchange_trips", &exchange_trips, py::arg("D"), py::arg("trips"), py::arg("demand"), py::arg("cap"),
+        py::arg("max_dist"), py::arg("move_cap") = py::none());
   m.def("astar_batch", &astar_batch, py::arg("indptr"), py::arg("indices"), py::arg("cost"),
         py::arg("lat"), py::arg("lon"), py::arg("src"), py::arg("dst"), py::arg("inv_vmax"),
         py::arg("threads") = 8);

@@ -291,6 +291,78 @@ static void fuzz_improve(std::mt19937_64& rng, int iters) {
   }
 }
 
+// route_core.h exchange_trips: on random matrices (asymmetric, with NaN / inf / negative entries),
+// random hand-made trips and random limits every stop stays exactly once, trips keep their depot
+// ends, no trip is created, the reported length is the measured one, every trip that changed passes
+// the greedy's float walks, and a search that ended on its own leaves nothing to a second call
+// (under the same limits; a third of the runs have none at all)
+static void fuzz_exchange(std::mt19937_64& rng, int iters) {
+  for (int it = 0; it < iters / 100; ++it) {
+    const int n1 = 2 + (int)(rng() % 30);
+    std::vector<double> d((size_t)n1 * n1, 0.0), dem(n1, 0.0);
+    for (int a = 0; a < n1; ++a)
+      for (int b = 0; b < n1; ++b)
+        if (a != b) d[(size_t)a * n1 + b] = 100.0 + (double)(rng() % 1000000) / 37.0;
+    if (rng() % 4 == 0 && n1 > 3) {
+      d[(size_t)1 * n1 + 2] = NAN;
+      d[(size_t)2 * n1 + 3] = INFINITY;
+      d[(size_t)3 * n1 + 1] = -5.0;
+    }
+    for (int s = 1; s < n1; ++s) dem[s] = (double)(1 + rng() % 3);
+    if (rng() % 16 == 0) dem[1 + rng() % (n1 - 1)] = rng() % 2 ? NAN : -1.0;   // the stage is skipped
+    // hand-made trips: a random permutation cut at random places (some trips empty)
+    std::vector<int> perm(n1 - 1);
+    for (int s = 1; s < n1; ++s) perm[s - 1] = s;
+    std::shuffle(perm.begin(), perm.end(), rng);
+    std::vector<std::vector<int>> trips(1, std::vector<int>{0});
+    for (int s : perm) {
+      if (rng() % 4 == 0) {
+        trips.back().push_back(0);
+        trips.push_back({0});
+      }
+      trips.back().push_back(s);
+    }
+    trips.back().push_back(0);
+    const std::vector<std::vector<int>> before = trips;
+    const bool free_run = rng() % 3 == 0;
+    const double cap = free_run ? 9e12 : (double)(2 + rng() % 30);
+    const double maxd = free_run ? 9e12 : (rng() % 8 == 0 ? NAN : 20000.0 + (double)(rng() % 400000));
+    const long long move_cap = rng() % 8 == 0 ? (long long)(rng() % 4) : -1;
+    const rtr::ExchangeStats st = rtr::exchange_trips(d, n1, dem, cap, maxd, trips, move_cap);
+    std::vector<int> seen(n1, 0);
+    long long len = 0;
+    for (const auto& t : trips) {
+      CHECK(t.size() >= 2 && t.front() == 0 && t.back() == 0, "exchange_trips broke a trip's ends");
+      for (size_t p = 1; p + 1 < t.size(); ++p)
+        if (t[p] >= 1 && t[p] < n1) ++seen[t[p]];
+      for (size_t p = 0; p + 1 < t.size(); ++p) len += rtr::improve_q(d[(size_t)t[p] * n1 + t[p + 1]]);
+      if (std::find(before.begin(), before.end(), t) == before.end()) {  // a changed trip: the greedy's walks
+        double s = 0.0, load = 0.0;
+        const int k = (int)t.size() - 2;
+        for (int p = 0; p < k; ++p) s += d[(size_t)t[p] * n1 + t[p + 1]];
+        for (int p = 1; p <= k; ++p) load += dem[t[p]];
+        CHECK(s + d[(size_t)t[k] * n1] <= maxd && load <= cap, "exchange_trips kept a trip that fails the float walks");
+      }
+    }
+    bool once = true;
+    for (int s = 1; s < n1; ++s) once = once && seen[s] == 1;
+    CHECK(once, "exchange_trips lost or repeated a stop");
+    CHECK(st.trips_before == (long long)before.size() && st.trips_after == (long long)trips.size() &&
+              st.trips_after <= st.trips_before,
+          "exchange_trips trip counts: %lld -> %lld, %zu -> %zu", st.trips_before, st.trips_after, before.size(), trips.size());
+    CHECK(len == st.len_after_q && st.len_after_q <= st.len_before_q, "exchange_trips: length after %lld, measured %lld, before %lld",
+          st.len_after_q, len, st.len_before_q);
+    CHECK(st.moves > 0 || trips == before || st.trips_after < st.trips_before, "exchange_trips changed trips without a move");
+    if (!st.rejected && move_cap < 0 && st.moves < 4LL * (n1 - 1)) {
+      std::vector<std::vector<int>> again = trips;
+      const rtr::ExchangeStats st2 = rtr::exchange_trips(d, n1, dem, cap, maxd, again, -1);
+      CHECK(st2.moves == 0 && again == trips, "exchange_trips left %lld moves", st2.moves);
+      CHECK(st2.len_before_q == st.len_after_q, "exchange_trips: length after %lld, measured again %lld", st.len_after_q,
+            st2.len_before_q);
+    }
+  }
+}
+
 // alternatives.h: via nodes stay in range, unique, within the detour band, and reproducible; the
 // argmin treats non-finite scores as +inf
 static void fuzz_alternatives(std::mt19937_64& rng, int iters) {
@@ -573,6 +645,7 @@ int main(int argc, char** argv) {
   fuzz_route(rng, iters);
   fuzz_coord_cache(rng, iters);
   fuzz_improve(rng, iters);
+  fuzz_exchange(rng, iters);
   fuzz_alternatives(rng, iters);
   fuzz_history(rng, iters);
   store_while_reading();

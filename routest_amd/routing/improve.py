@@ -154,7 +154,14 @@ def improve_trips(d, trips: Sequence[Sequence[int]], max_dist: float
 
 
 def improvement_properties(stats: Dict[str, int]) -> Dict[str, object]:
-    """``properties.improvement`` of a response, from the statistics of :func:`improve_trips`."""
+    """``properties.improvement`` of a response, from the statistics of :func:`improve_trips`, or
+    from the composed statistics of an ``exchange`` request (:mod:`routing.exchange`)."""
+    if "exchange_moves" in stats:
+        return {"method": METHOD + "+exchange", "moves": int(stats["moves"]),
+                "exchange_moves": int(stats["exchange_moves"]),
+                "trips_before": int(stats["trips_before"]), "trips_after": int(stats["trips_after"]),
+                "matrix_distance_before": int(stats["len_before_q"]) / 1000.0,
+                "matrix_distance_after": int(stats["len_after_q"]) / 1000.0}
     return {"method": METHOD, "moves": int(stats["moves"]),
             "trips_changed": int(stats["trips_changed"]),
             "matrix_distance_before": int(stats["len_before_q"]) / 1000.0,

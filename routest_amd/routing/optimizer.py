@@ -18,6 +18,8 @@ Opt-in (``"improve": true`` on a multi-stop request, JSON ``true`` exactly): eve
 greedy is re-sequenced by the intra-trip 2-opt / Or-opt of :mod:`routing.improve` before the legs
 are routed, and ``properties.improvement`` reports what it did.  Single-destination requests and
 ``alternatives`` requests ignore the field; without it every response is unchanged.
+``"exchange": true`` (same rule; it implies ``improve``) adds the inter-trip relocate / swap search
+of :mod:`routing.exchange` between two such passes; the answer may then hold fewer trips.
 The batched GPU path for many concurrent requests (K5 + K6) is :func:`optimize_many`.
 """
 from __future__ import annotations
@@ -27,6 +29,7 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 
 from .greedy import InfeasibleStops, greedy_trips, optimized_order
+from .exchange import improve_exchange_trips, wants_exchange
 from .improve import improve_trips, improvement_properties, wants_improve
 from .providers import ProviderError, _bbox, profile_for
 
@@ -110,9 +113,10 @@ def assemble_trips(provider, all_points: List[Dict[str, Any]], trips: List[List[
 
 def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, Any],
                trips: Optional[List[List[int]]] = None, ctx=None, improve: bool = False,
-               improvement: Optional[Dict[str, int]] = None) -> Dict[str, Any]:
-    """``improve``: re-sequence the trips built here (routing/improve.py).  Trips given by the
-    caller are taken as they are; ``improvement`` holds their statistics if they were improved."""
+               improvement: Optional[Dict[str, int]] = None, exchange: bool = False) -> Dict[str, Any]:
+    """``improve``: re-sequence the trips built here (routing/improve.py); ``exchange``: also move
+    stops between them (routing/exchange.py; it implies ``improve``).  Trips given by the caller
+    are taken as they are; ``improvement`` holds their statistics if they were improved."""
     all_points = [source] + list(destinations)
     if trips is None:
         try:
@@ -127,7 +131,9 @@ def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, A
             trips = greedy_trips(dm.tolist(), demand, cap, max_dist)
         except InfeasibleStops as e:
             return {"error": str(e)}
-        if improve:
+        if exchange:
+            trips, improvement = improve_exchange_trips(dm, trips, demand, cap, max_dist)
+        elif improve:
             trips, improvement = improve_trips(dm, trips, max_dist)
     feature = assemble_trips(provider, all_points, trips, profile, source, destinations, ctx)
     if improvement is not None and "error" not in feature:
@@ -168,7 +174,8 @@ def optimize_route(input_data: Any, provider, engine: str = "backend:mi355x",
         _annotate(feature, driver, vehicle_type, engine)
         return feature
     feature = multi_stop(provider, source, destinations, profile, driver, trips, ctx,
-                         improve=wants_improve(input_data), improvement=improvement)
+                         improve=wants_improve(input_data), improvement=improvement,
+                         exchange=wants_exchange(input_data))
     if "error" in feature:
         return feature
     _annotate(feature, driver, vehicle_type, engine)
@@ -188,7 +195,8 @@ def optimize_many(requests: Sequence[Dict[str, Any]], provider, engine: str = "b
     stat_map: Dict[int, Any] = {}
     if multi and getattr(provider, "name", "") == "haversine":
         res, stats = batched_trips([requests[i] for i in multi], circuity=provider.circuity,
-                                   device=device, improve=[wants_improve(requests[i]) for i in multi])
+                                   device=device, improve=[wants_improve(requests[i]) for i in multi],
+                                   exchange=[wants_exchange(requests[i]) for i in multi])
         trip_map = dict(zip(multi, res))
         stat_map = dict(zip(multi, stats))
     out = []

@@ -38,6 +38,7 @@ from ..utils.metrics import REGISTRY
 from ..utils.queues import get_until
 from .batched import batched_trips
 from .greedy import InfeasibleStops
+from .exchange import wants_exchange
 from .improve import wants_improve
 from .optimizer import optimize_route
 from .providers import ProviderError
@@ -150,7 +151,8 @@ class RouteBatcher:
         (and point-to-point request) in ONE leg launch.  Each context group runs start to finish
         under a pin of its metric, and its edge costs are copied to the host then, so a flush with
         more contexts than the metric cache holds never loses one in between.  Requests that ask
-        for ``improve`` get their trips re-sequenced right after K6 (K6b), before the legs.  Returns
+        for ``improve`` / ``exchange`` get their trips improved right after K6 (K6b, K6c), before the
+        legs.  Returns
         (trips by request, legs dict, host edge costs by metric key, improvement stats by request)."""
         prov = self.provider
         trips: Dict[int, Any] = {}
@@ -192,7 +194,8 @@ class RouteBatcher:
                 n = len(pts[k])
                 D[i, :n, :n] = met
             res, st = batched_trips([payloads[k] for k in multi], device=device, D=D,
-                                    improve=[wants_improve(payloads[k]) for k in multi])
+                                    improve=[wants_improve(payloads[k]) for k in multi],
+                                    exchange=[wants_exchange(payloads[k]) for k in multi])
             trips.update(zip(multi, res))
             stats.update(zip(multi, st))
         pairs = set()
@@ -264,7 +267,8 @@ class RouteBatcher:
         multi = [k for k, r in enumerate(payloads) if _valid_points(r) and len(r["destination_points"]) > 1]
         if multi and name in ("haversine", "graph"):
             res, st = batched_trips([payloads[k] for k in multi], circuity=self.provider.circuity,
-                                    device=device, improve=[wants_improve(payloads[k]) for k in multi])
+                                    device=device, improve=[wants_improve(payloads[k]) for k in multi],
+                                    exchange=[wants_exchange(payloads[k]) for k in multi])
             trips = dict(zip(multi, res))
             stats = dict(zip(multi, st))
         if name == "graph":
