@@ -548,6 +548,70 @@ std::vector<torch::Tensor> route_exchange_trips(torch::Tensor D, torch::Tensor n
   return {moves, rejected, tbefore, tafter, before, after};
 }
 
+// K10 candidates: (cand i32 [P,k], cand_d2 i64 [P,k], n_cand i32 [P]) of the fixes (py, px) on the
+// graph's bucket grid (routing/mapmatch.py build_grid).
+std::vector<torch::Tensor> mm_candidates(torch::Tensor start, torch::Tensor items, torch::Tensor nqy,
+                                         torch::Tensor nqx, int64_t y0, int64_t x0, int64_t cell, int64_t ny,
+                                         int64_t nx, torch::Tensor py, torch::Tensor px, int64_t radius_cm,
+                                         int64_t k) {
+  for (auto* t : {&start, &items, &nqy, &nqx, &py, &px}) check_dev(*t, "map-matching tensor");
+  const int64_t N = items.numel(), P = py.numel();
+  TORCH_CHECK(N >= 1 && N < (1LL << 30), "node ids must be below 2^30");
+  TORCH_CHECK(cell >= 1 && ny >= 1 && nx >= 1 && ny * nx < (1LL << 31), "grid shape");
+  TORCH_CHECK(start.scalar_type() == torch::kInt32 && start.numel() == ny * nx + 1, "start must be i32 [ny*nx+1]");
+  TORCH_CHECK(items.scalar_type() == torch::kInt32, "items must be i32 [N]");
+  TORCH_CHECK(nqy.scalar_type() == torch::kInt64 && nqy.numel() == N && nqx.scalar_type() == torch::kInt64 &&
+                  nqx.numel() == N, "nqy / nqx must be i64 [N]");
+  TORCH_CHECK(py.scalar_type() == torch::kInt64 && px.scalar_type() == torch::kInt64 && px.numel() == P,
+              "py / px must be i64 [P]");
+  TORCH_CHECK(P < (1LL << 29), "too many fixes");
+  TORCH_CHECK(k >= 1 && k <= 16, "k must be in 1..16");
+  TORCH_CHECK(radius_cm >= 1 && radius_cm <= 100000, "radius must be in 1..100000 cm");
+  const c10::DeviceGuard guard(py.device());
+  auto cand = torch::empty({P, k}, py.options().dtype(torch::kInt32));
+  auto cand_d2 = torch::empty({P, k}, py.options());
+  auto n_cand = torch::empty({P}, py.options().dtype(torch::kInt32));
+  RT_CHECK_HIP(rt::launch_mm_candidates(
+      start.data_ptr<int>(), items.data_ptr<int>(), (const long long*)nqy.data_ptr<int64_t>(),
+      (const long long*)nqx.data_ptr<int64_t>(), (int)N, (long long)y0, (long long)x0, (long long)cell, (int)ny,
+      (int)nx, (const long long*)py.data_ptr<int64_t>(), (const long long*)px.data_ptr<int64_t>(), (int)P,
+      (long long)radius_cm, (int)k, cand.data_ptr<int>(), (long long*)cand_d2.data_ptr<int64_t>(),
+      n_cand.data_ptr<int>(), cur_stream(py)));
+  return {cand, cand_d2, n_cand};
+}
+
+// K10 Viterbi: (choice i32 [B,T], segment i32 [B,T], n_segments i32 [B], cost i64 [B]).
+std::vector<torch::Tensor> mm_viterbi(torch::Tensor cand_d2, torch::Tensor n_cand, torch::Tensor route_cm,
+                                      torch::Tensor g, torch::Tensor npts, int64_t beta_cm, int64_t sigma_cm,
+                                      int64_t max_detour_cm) {
+  for (auto* t : {&cand_d2, &n_cand, &route_cm, &g, &npts}) check_dev(*t, "map-matching tensor");
+  TORCH_CHECK(cand_d2.scalar_type() == torch::kInt64 && cand_d2.dim() == 3, "cand_d2 must be i64 [B,T,K]");
+  const int64_t B = cand_d2.size(0), T = cand_d2.size(1), K = cand_d2.size(2);
+  TORCH_CHECK(T >= 1 && T <= 2048, "at most 2048 fixes per trace");
+  TORCH_CHECK(K >= 1 && K <= 16, "K must be in 1..16");
+  TORCH_CHECK(B < (1LL << 31), "too many traces");
+  TORCH_CHECK(n_cand.scalar_type() == torch::kInt32 && n_cand.numel() == B * T, "n_cand must be i32 [B,T]");
+  TORCH_CHECK(route_cm.scalar_type() == torch::kInt64 && route_cm.numel() == B * (T - 1) * K * K,
+              "route_cm must be i64 [B,T-1,K,K]");
+  TORCH_CHECK(g.scalar_type() == torch::kInt64 && g.numel() == B * (T - 1), "g must be i64 [B,T-1]");
+  TORCH_CHECK(npts.scalar_type() == torch::kInt32 && npts.numel() == B, "npts must be i32 [B]");
+  TORCH_CHECK(beta_cm >= 1 && beta_cm <= 10000 && sigma_cm >= 1 && sigma_cm <= 20000 && max_detour_cm >= 1 &&
+                  max_detour_cm <= 500000, "beta 1..1e4, sigma 1..2e4, max_detour 1..5e5 cm");
+  const c10::DeviceGuard guard(cand_d2.device());
+  auto iopt = cand_d2.options().dtype(torch::kInt32);
+  auto choice = torch::empty({B, T}, iopt);
+  auto seg = torch::empty({B, T}, iopt);
+  auto nseg = torch::empty({B}, iopt);
+  auto cost = torch::empty({B}, cand_d2.options());
+  RT_CHECK_HIP(rt::launch_mm_viterbi(
+      (const long long*)cand_d2.data_ptr<int64_t>(), n_cand.data_ptr<int>(),
+      (const long long*)route_cm.data_ptr<int64_t>(), (const long long*)g.data_ptr<int64_t>(), npts.data_ptr<int>(),
+      (int)B, (int)T, (int)K, (long long)beta_cm, (long long)sigma_cm, (long long)max_detour_cm,
+      choice.data_ptr<int>(), seg.data_ptr<int>(), nseg.data_ptr<int>(), (long long*)cost.data_ptr<int64_t>(),
+      cur_stream(cand_d2)));
+  return {choice, seg, nseg, cost};
+}
+
 rt::NormParams norm_from(const std::vector<double>& norm) {
   TORCH_CHECK(norm.size() == 8, "norm must hold 4 scales + 4 shifts");
   rt::NormParams np;
@@ -1495,6 +1559,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K6c: inter-trip relocate / swap on K6's outputs (visit, trip_of, ntrips rewritten in place)",
         py::arg("D"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"), py::arg("visit"),
         py::arg("trip_of"), py::arg("ntrips"), py::arg("status"), py::arg("flag"), py::arg("move_cap") = -1);
+  m.def("mm_candidates", &mm_candidates, "K10: map-matching candidates of GPS fixes on the bucket grid",
+        py::arg("start"), py::arg("items"), py::arg("nqy"), py::arg("nqx"), py::arg("y0"), py::arg("x0"),
+        py::arg("cell"), py::arg("ny"), py::arg("nx"), py::arg("py"), py::arg("px"), py::arg("radius_cm"),
+        py::arg("k"));
+  m.def("mm_viterbi", &mm_viterbi, "K10: segmenting Viterbi of the map matcher over given costs",
+        py::arg("cand_d2"), py::arg("n_cand"), py::arg("route_cm"), py::arg("g"), py::arg("npts"),
+        py::arg("beta_cm"), py::arg("sigma_cm"), py::arg("max_detour_cm"));
   m.def("big_layer1", &big_layer1, "wide MLP: featurize + layer 1 -> h1 (hperm order)",
         py::arg("records"), py::arg("w1p"), py::arg("H"), py::arg("norm"), py::arg("h1"),
         py::arg("xf") = py::none(), py::arg("mbits") = py::none());

@@ -241,6 +241,22 @@ hipError_t launch_exchange_trips(const double* D, const int* npts, const double*
                                  int* trips_before, int* trips_after, long long* len_before_q,
                                  long long* len_after_q, hipStream_t stream);
 
+// ---- K10 GPS-trace map matching : map_match.hip ----
+// Integer-only (centimetres quantized by the caller, routing/mapmatch.py).  Candidates: per fix the
+// k nodes within radius_cm with the smallest (d2, node id) from the bucket grid (start [ny*nx+1],
+// items [N], node coordinates nqy / nqx [N]); cand / cand_d2 [P, k] are -1 padded.
+hipError_t launch_mm_candidates(const int* start, const int* items, const long long* nqy, const long long* nqx,
+                                int N, long long y0, long long x0, long long cell, int ny, int nx,
+                                const long long* py, const long long* px, int P, long long radius_cm, int k,
+                                int* cand, long long* cand_d2, int* n_cand, hipStream_t stream);
+// The segmenting Viterbi over given costs: cand_d2 [B,T,K], n_cand [B,T] (clamped to 1..K),
+// route_cm [B,T-1,K,K] (-1 infeasible), g [B,T-1], npts [B]; choice / seg [B,T] (-1 from npts on),
+// nseg [B], cost [B] (the sum of the segments' final scores).
+hipError_t launch_mm_viterbi(const long long* cand_d2, const int* n_cand, const long long* route_cm,
+                             const long long* g, const int* npts, int B, int T, int K, long long beta_cm,
+                             long long sigma_cm, long long max_detour_cm, int* choice, int* seg, int* nseg,
+                             long long* cost, hipStream_t stream);
+
 // ---- persistent single-request scorer : persistent_serve.hip ----
 struct PersistentScorer;
 PersistentScorer* pscore_create(int device, const void* blob, int H, const NormParams& np, int cap,

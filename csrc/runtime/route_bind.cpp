@@ -8,6 +8,8 @@
 //    reference the GPU service is tested against, and a fast path for GPU-less deployments.
 //  * route_assemble_graph: graph-provider assembly from given trips + searched legs (tests);
 //    `improvement`: the statistics of trips that were improved (routing/improve.py).
+//  * MmGrid / mm_viterbi: the host reference of the map matcher (map_match.h; the definition is in
+//    routing/mapmatch.py, the HIP kernels in csrc/map_match.hip).
 //  * RouteStore / RowId: the route service's SQLite writer (route_store.h) over requests assembled
 //    by the two functions above (as_row=True) — its CPU tests.
 #include <pybind11/numpy.h>
@@ -20,6 +22,7 @@
 
 #include "alternatives.h"
 #include "history_db.h"
+#include "map_match.h"
 #include "route_core.h"
 #include "route_record.h"
 #include "route_store.h"
@@ -84,6 +87,78 @@ class PyNodeGrid {
   rtr::NodeGrid g_;
   double c_;
 };
+
+// map_match.h: the bucket grid over a graph's quantized node coordinates and its radius queries
+class PyMmGrid {
+ public:
+  PyMmGrid(py::array_t<int64_t, py::array::c_style | py::array::forcecast> qy,
+           py::array_t<int64_t, py::array::c_style | py::array::forcecast> qx) {
+    if (qy.ndim() != 1 || qx.ndim() != 1 || qy.shape(0) != qx.shape(0)) throw std::invalid_argument("qy/qx mismatch");
+    g_.build(qy.data(), qx.data(), (size_t)qy.shape(0));
+  }
+  py::tuple candidates(py::array_t<int64_t, py::array::c_style | py::array::forcecast> py_,
+                       py::array_t<int64_t, py::array::c_style | py::array::forcecast> px_, int64_t radius_cm,
+                       int k) const {
+    if (py_.ndim() != 1 || px_.ndim() != 1 || py_.shape(0) != px_.shape(0)) throw std::invalid_argument("py/px mismatch");
+    if (k < 1 || k > rtr::kMmMaxK) throw std::invalid_argument("k in 1..16");
+    const py::ssize_t P = py_.shape(0);
+    py::array_t<int32_t> cand({P, (py::ssize_t)k});
+    py::array_t<int64_t> d2({P, (py::ssize_t)k});
+    py::array_t<int32_t> n(P);
+    {
+      const int64_t* a = py_.data();
+      const int64_t* b = px_.data();
+      int32_t* c = cand.mutable_data();
+      int64_t* d = d2.mutable_data();
+      int32_t* e = n.mutable_data();
+      py::gil_scoped_release nogil;
+      rtr::mm_candidates(g_, a, b, (size_t)P, radius_cm, k, c, d, e);
+    }
+    return py::make_tuple(cand, d2, n);
+  }
+
+ private:
+  rtr::MmGrid g_;
+};
+
+// (choice i32 [B, T], segment i32 [B, T], n_segments i32 [B], cost i64 [B])
+py::tuple py_mm_viterbi(py::array_t<int64_t, py::array::c_style | py::array::forcecast> cand_d2,
+                        py::array_t<int32_t, py::array::c_style | py::array::forcecast> n_cand,
+                        py::array_t<int64_t, py::array::c_style | py::array::forcecast> route_cm,
+                        py::array_t<int64_t, py::array::c_style | py::array::forcecast> g,
+                        py::array_t<int32_t, py::array::c_style | py::array::forcecast> npts, int64_t beta_cm,
+                        int64_t sigma_cm, int64_t max_detour_cm) {
+  if (cand_d2.ndim() != 3) throw std::invalid_argument("cand_d2 must be [B, T, K]");
+  const py::ssize_t B = cand_d2.shape(0), T = cand_d2.shape(1), K = cand_d2.shape(2);
+  if (K < 1 || K > rtr::kMmMaxK || T < 1 || T > rtr::kMmMaxPoints) throw std::invalid_argument("K in 1..16, T in 1..2048");
+  if (n_cand.ndim() != 2 || n_cand.shape(0) != B || n_cand.shape(1) != T) throw std::invalid_argument("n_cand must be [B, T]");
+  if (route_cm.ndim() != 4 || route_cm.shape(0) != B || route_cm.shape(1) != T - 1 || route_cm.shape(2) != K ||
+      route_cm.shape(3) != K)
+    throw std::invalid_argument("route_cm must be [B, T-1, K, K]");
+  if (g.ndim() != 2 || g.shape(0) != B || g.shape(1) != T - 1) throw std::invalid_argument("g must be [B, T-1]");
+  if (npts.ndim() != 1 || npts.shape(0) != B) throw std::invalid_argument("npts must be [B]");
+  const rtr::MmCosts c{beta_cm, sigma_cm, max_detour_cm};
+  rtr::mm_check_costs(c);
+  py::array_t<int32_t> choice({B, T}), seg({B, T});
+  py::array_t<int32_t> nseg(B);
+  py::array_t<int64_t> cost(B);
+  {
+    const int64_t* cd = cand_d2.data();
+    const int32_t* nc = n_cand.data();
+    const int64_t* rc = route_cm.data();
+    const int64_t* gg = g.data();
+    const int32_t* np = npts.data();
+    int32_t* ch = choice.mutable_data();
+    int32_t* sg = seg.mutable_data();
+    int32_t* ns = nseg.mutable_data();
+    int64_t* co = cost.mutable_data();
+    py::gil_scoped_release nogil;
+    for (py::ssize_t b = 0; b < B; ++b)
+      co[b] = rtr::mm_viterbi(cd + b * T * K, nc + b * T, rc + b * (T - 1) * K * K, gg + b * (T - 1), (int)T, (int)K,
+                              np[b], c, ch + b * T, sg + b * T, ns + b);
+  }
+  return py::make_tuple(choice, seg, nseg, cost);
+}
 
 // Maneuvers of graph legs (route_core.h leg_steps) for the Python GraphProvider: the graph's
 // arrays are held once; per call the leg's node path, seconds and the context's edge costs.
@@ -469,6 +544,21 @@ void bind_route(py::module& m) {
       .def(py::init<py::array_t<double, py::array::c_style | py::array::forcecast>,
                     py::array_t<double, py::array::c_style | py::array::forcecast>, double>())
       .def("nearest", &PyNodeGrid::nearest);
+  py::class_<PyMmGrid>(m, "MmGrid")
+      .def(py::init<py::array_t<int64_t, py::array::c_style | py::array::forcecast>,
+                    py::array_t<int64_t, py::array::c_style | py::array::forcecast>>(),
+           py::arg("qy"), py::arg("qx"))
+      .def("candidates", &PyMmGrid::candidates, py::arg("py"), py::arg("px"), py::arg("radius_cm"), py::arg("k"));
+  m.def("mm_candidates",   // one-off form: builds the grid for this call
+        [](py::array_t<int64_t, py::array::c_style | py::array::forcecast> qy,
+           py::array_t<int64_t, py::array::c_style | py::array::forcecast> qx,
+           py::array_t<int64_t, py::array::c_style | py::array::forcecast> py_,
+           py::array_t<int64_t, py::array::c_style | py::array::forcecast> px_, int64_t radius_cm, int k) {
+          return PyMmGrid(qy, qx).candidates(py_, px_, radius_cm, k);
+        },
+        py::arg("qy"), py::arg("qx"), py::arg("py"), py::arg("px"), py::arg("radius_cm"), py::arg("k"));
+  m.def("mm_viterbi", &py_mm_viterbi, py::arg("cand_d2"), py::arg("n_cand"), py::arg("route_cm"), py::arg("g"),
+        py::arg("npts"), py::arg("beta_cm"), py::arg("sigma_cm"), py::arg("max_detour_cm"));
   m.def("route_optimize_cpu", &route_optimize_cpu, py::arg("body"), py::arg("json_ok") = true,
         py::arg("engine") = "backend:mi355x", py::arg("circuity") = 1.3, py::arg("step_m") = 150.0,
         py::arg("is_request_route") = false, py::arg("compat200") = true, py::arg("as_row") = false);

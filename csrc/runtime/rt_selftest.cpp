@@ -2,7 +2,8 @@
 // route service's host code (route_core.h: route-request parsing, Python-exact float fast paths;
 // alternatives.h: via-node candidates and scores; route_store.h + history_db.h: the route service's
 // SQLite writer fills a database with fuzzed rows, the native history reads run over it with
-// fuzzed limits / ids, and the two run against each other on two threads).
+// fuzzed limits / ids, and the two run against each other on two threads; map_match.h: the map
+// matcher's candidate search against a scan and its Viterbi against full enumeration).
 // Built with -fsanitize=address,undefined by `tools/build_ext.py --sanitize` or the CMake `asan`
 // preset (the reference has no race detection / sanitizers at all), and run by
 // tests/test_sanitize_cpu.py.  Exit code 0 = all invariants held and no sanitizer report.
@@ -25,6 +26,7 @@
 
 #include "alternatives.h"
 #include "history_db.h"
+#include "map_match.h"
 #include "route_core.h"
 #include "route_store.h"
 #include "rt_core.h"
@@ -363,6 +365,156 @@ static void fuzz_exchange(std::mt19937_64& rng, int iters) {
   }
 }
 
+// map_match.h mm_candidates: on random node sets (clusters, duplicates, one line) and fixes inside,
+// on and far outside the grid the answer equals a scan of all nodes sorted by (d2, node id)
+static void fuzz_mm_candidates(std::mt19937_64& rng, int iters) {
+  for (int it = 0; it < iters / 200; ++it) {
+    const size_t n = 1 + rng() % 400;
+    const int64_t span = 1 + (int64_t)(rng() % 3000000), ox = (int64_t)(rng() % 4000000000ULL) - 2000000000LL;
+    const bool line = rng() % 8 == 0;
+    std::vector<int64_t> qy(n), qx(n);
+    for (size_t i = 0; i < n; ++i) {
+      qy[i] = 162000000 + (int64_t)(rng() % span);
+      qx[i] = line ? ox : ox + (int64_t)(rng() % span);
+      if (i && rng() % 16 == 0) {   // a node on top of another one
+        qy[i] = qy[i - 1];
+        qx[i] = qx[i - 1];
+      }
+    }
+    rtr::MmGrid g;
+    g.build(qy.data(), qx.data(), n);
+    CHECK(g.start.back() == (int32_t)n && (int64_t)g.ny * g.nx < 5000000, "MmGrid: %d x %d cells", g.ny, g.nx);
+    const size_t P = 1 + rng() % 40;
+    const int k = 1 + (int)(rng() % 16);
+    const int64_t radius = 1 + (int64_t)(rng() % 100000);
+    std::vector<int64_t> py(P), px(P);
+    for (size_t p = 0; p < P; ++p) {
+      const size_t v = rng() % n;
+      switch (rng() % 4) {
+        case 0: py[p] = qy[v]; px[p] = qx[v]; break;                                     // on a node
+        case 1: py[p] = qy[v] + radius; px[p] = qx[v]; break;                            // exactly at the radius
+        case 2: py[p] = qy[v] + (int64_t)(rng() % 4000000) - 2000000; px[p] = qx[v] - 3 * radius; break;
+        default: py[p] = qy[v] + (int64_t)(rng() % (2 * radius + 1)) - radius;
+                 px[p] = qx[v] + (int64_t)(rng() % (2 * radius + 1)) - radius; break;
+      }
+    }
+    std::vector<int32_t> cand(P * k), nc(P);
+    std::vector<int64_t> d2(P * k);
+    rtr::mm_candidates(g, py.data(), px.data(), P, radius, k, cand.data(), d2.data(), nc.data());
+    for (size_t p = 0; p < P; ++p) {
+      std::vector<std::pair<int64_t, int32_t>> all;
+      for (size_t v = 0; v < n; ++v) {
+        const int64_t dy = qy[v] - py[p], dx = qx[v] - px[p];
+        if (std::llabs(dy) <= radius && std::llabs(dx) <= radius && dy * dy + dx * dx <= radius * radius)
+          all.emplace_back(dy * dy + dx * dx, (int32_t)v);
+      }
+      std::sort(all.begin(), all.end());
+      const size_t want = std::min(all.size(), (size_t)k);
+      bool same = nc[p] == (int32_t)want;
+      for (size_t j = 0; same && j < (size_t)k; ++j)
+        same = j < want ? (cand[p * k + j] == all[j].second && d2[p * k + j] == all[j].first)
+                        : (cand[p * k + j] == -1 && d2[p * k + j] == -1);
+      CHECK(same, "mm_candidates differs from the scan (n=%zu k=%d radius=%lld fix %zu)", n, k, (long long)radius, p);
+    }
+  }
+}
+
+// map_match.h mm_viterbi: on random costs (infeasible routes, detours beyond the limit, equal
+// costs, costs at the parameter maxima) the result is a valid segmentation — choices inside
+// n_cand, segment indices rising by at most one, feasible transitions inside a segment, none
+// possible from the previous segment's live end across a break — the reported cost is the chosen
+// states' own cost, and for short traces it is the minimum over all state sequences
+static void fuzz_mm_viterbi(std::mt19937_64& rng, int iters) {
+  for (int it = 0; it < iters / 50; ++it) {
+    const bool tiny = it % 2 == 0;
+    const int T = tiny ? 1 + (int)(rng() % 5) : 1 + (int)(rng() % 80);
+    const int K = tiny ? 1 + (int)(rng() % 3) : 1 + (int)(rng() % 16);
+    const int n = rng() % 8 == 0 ? (int)(rng() % (T + 1)) : T;
+    const bool maxed = rng() % 4 == 0;
+    const rtr::MmCosts c{maxed ? 10000 : 1 + (int64_t)(rng() % 10000), maxed ? 20000 : 1 + (int64_t)(rng() % 20000),
+                         maxed ? 500000 : 1 + (int64_t)(rng() % 500000)};
+    const int64_t coarse = rng() % 2 ? 1 : 1 + c.max_detour_cm / 3;   // coarse values make equal costs
+    std::vector<int64_t> cd((size_t)T * K), route((size_t)(T > 1 ? T - 1 : 0) * K * K), g(T > 1 ? T - 1 : 0);
+    std::vector<int32_t> nc(T);
+    for (auto& v : cd) v = maxed ? 10000000000LL : (int64_t)(rng() % 1000) * coarse;
+    for (auto& v : nc) v = 1 + (int32_t)(rng() % K);
+    for (auto& v : g) v = (int64_t)(rng() % 300000);
+    const int infeasible = (int)(rng() % 4);
+    for (size_t e = 0; e < route.size(); ++e) {
+      const int64_t gt = g[e / ((size_t)K * K)];
+      if (infeasible == 3 || (infeasible && rng() % (infeasible == 1 ? 8 : 2) == 0)) route[e] = -1;
+      else if (maxed) route[e] = gt + c.max_detour_cm + (rng() % 8 == 0);
+      else route[e] = std::max<int64_t>(0, gt + ((int64_t)(rng() % 5) - 2) * coarse * (1 + (int64_t)(rng() % 3)));
+    }
+    std::vector<int32_t> choice(T), seg(T);
+    int32_t nseg = 0;
+    const int64_t cost = rtr::mm_viterbi(cd.data(), nc.data(), route.data(), g.data(), T, K, n, c, choice.data(),
+                                         seg.data(), &nseg);
+    auto trans = [&](int t, int i, int j) -> int64_t {   // -1 infeasible
+      const int64_t r = route[((size_t)(t - 1) * K + i) * K + j];
+      if (r < 0) return -1;
+      const int64_t dev = r > g[t - 1] ? r - g[t - 1] : g[t - 1] - r;
+      return dev > c.max_detour_cm ? -1 : 2 * c.sigma_cm * c.sigma_cm * dev;
+    };
+    int64_t own = 0;
+    bool ok = n == 0 ? nseg == 0 : nseg >= 1;
+    for (int t = 0; ok && t < T; ++t) {
+      if (t >= n) {
+        ok = choice[t] == -1 && seg[t] == -1;
+        continue;
+      }
+      ok = choice[t] >= 0 && choice[t] < nc[t] && seg[t] == (t == 0 ? 0 : seg[t - 1]) + (t && seg[t] != seg[t - 1]);
+      if (!ok) break;
+      own += c.beta_cm * cd[(size_t)t * K + choice[t]];
+      if (t && seg[t] == seg[t - 1]) {
+        const int64_t tr = trans(t, choice[t - 1], choice[t]);
+        ok = tr >= 0;
+        own += tr;
+      } else if (t) {   // a break: the chosen end of the previous segment reaches nothing here
+        for (int j = 0; ok && j < nc[t]; ++j) ok = trans(t, choice[t - 1], j) < 0;
+      }
+    }
+    CHECK(ok && (n == 0 || seg[n - 1] == nseg - 1), "mm_viterbi: not a valid segmentation (T=%d K=%d n=%d)", T, K, n);
+    CHECK(!ok || own == cost, "mm_viterbi: cost %lld, the chosen states cost %lld", (long long)cost, (long long)own);
+    if (tiny && ok && n > 0) {   // full enumeration, segment by segment
+      int64_t total = 0;
+      int a = 0, segs = 0;
+      while (a < n) {
+        // the longest stretch from a that some state sequence survives, and its cheapest sequence
+        int reach = a;
+        int64_t best_at[6];
+        std::vector<int> s(n - a, 0);
+        for (int q = 0; q < 6; ++q) best_at[q] = -1;
+        for (;;) {
+          int64_t sum = 0;
+          int len = 0;
+          for (int t = a; t < n; ++t) {
+            if (s[t - a] >= nc[t]) break;
+            if (t > a) {
+              const int64_t tr = trans(t, s[t - 1 - a], s[t - a]);
+              if (tr < 0) break;
+              sum += tr;
+            }
+            sum += c.beta_cm * cd[(size_t)t * K + s[t - a]];
+            ++len;
+            if (best_at[len] < 0 || sum < best_at[len]) best_at[len] = sum;
+          }
+          int d = 0;
+          while (d < n - a && ++s[d] == K) s[d++] = 0;
+          if (d == n - a) break;
+        }
+        for (int len = 1; len <= n - a; ++len)
+          if (best_at[len] >= 0) reach = a + len;
+        total += best_at[reach - a];
+        a = reach;
+        ++segs;
+      }
+      CHECK(total == cost && segs == nseg, "mm_viterbi: cost %lld in %d segments, enumeration %lld in %d",
+            (long long)cost, nseg, (long long)total, segs);
+    }
+  }
+}
+
 // alternatives.h: via nodes stay in range, unique, within the detour band, and reproducible; the
 // argmin treats non-finite scores as +inf
 static void fuzz_alternatives(std::mt19937_64& rng, int iters) {
@@ -648,6 +800,8 @@ int main(int argc, char** argv) {
   fuzz_exchange(rng, iters);
   fuzz_alternatives(rng, iters);
   fuzz_history(rng, iters);
+  fuzz_mm_candidates(rng, iters);
+  fuzz_mm_viterbi(rng, iters);
   store_while_reading();
   threaded_pack_format(20000);
   std::printf("rt_selftest: %d iterations, %d failures\n", iters, g_fail);

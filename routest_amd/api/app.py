@@ -522,6 +522,27 @@ def create_app(services: Optional[Services] = None, settings: Optional[Settings]
             return JSONResponse({"error": str(e)}, 400)
         return JSONResponse(res, 200)
 
+    @app.post("/api/match")
+    async def match(request: Request):
+        """Map-match GPS traces to the road graph under the request's context (OSRM's match shape
+        per trace; routing/mapmatch.py): ``matchings`` (one connected node path per segment) and
+        ``tracepoints`` (one per fix, null when unmatched)."""
+        body = await _json_body(request, silent=False)
+        if isinstance(body, Response):
+            return body
+        if getattr(sv.provider, "name", "") != "graph" or not hasattr(sv.provider, "match"):
+            return JSONResponse({"error": "map matching needs the road graph: start the service with "
+                                          "ROUTEST_PROVIDER=graph"}, 400)
+        from ..routing.cch import RouteContext
+        from ..routing.mapmatch import match_response
+        from ..routing.providers import ProviderError
+        try:
+            res = await run_in_threadpool(match_response, sv.provider, body, RouteContext.from_request(body),
+                                          sv.route_device)
+        except (ValueError, ProviderError) as e:
+            return JSONResponse({"error": str(e)}, 400)
+        return JSONResponse(res, 200)
+
     # ------------------------------------------------------------------ ETA
     async def _predict_one(body: Dict[str, Any]):
         summary = body.get("summary") or {}

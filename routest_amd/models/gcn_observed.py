@@ -13,6 +13,8 @@ learns what the edge-cost model does not know, from trip observations:
 * **Observations**: trips between random node pairs, driven along the time-shortest path or (half
   of them) through a random via node, each observed once with its total time — the shape of what
   ``/api/update_tracker`` receives (RO/Flaskr/routes.py tracker: route + duration per trip).
+  A driver's phone sends GPS fixes, not node ids: :func:`trips_from_traces` turns traces and their
+  observed durations into this shape by map matching (routing/mapmatch.py).
 * **Model**: the GCN's node output is a delay factor ``delay(v) = 0.5 + softplus(.)``; the route's
   predicted hidden seconds are ``sum_i (delay(v_i) - 0.5) |v_i v_{i+1}| / V_REF``.  The loss is the
   mean squared error between that and each observed trip's residual (observed - edge-cost seconds):
@@ -199,6 +201,27 @@ class Observations:
         return {"nodes": torch.from_numpy(self.nodes).to(d), "trip": torch.from_numpy(self.trip).to(d),
                 "dseg": torch.from_numpy(self.dseg.astype(np.float32)).to(d),
                 "residual": torch.from_numpy(self.residual.astype(np.float32)).to(d)}
+
+
+def trips_from_traces(provider, traces: Sequence[Any], observed_seconds: Sequence[float], ctx=None, params=None,
+                      device=None) -> Tuple[List[Tuple[List[int], float]], List[int]]:
+    """Observed trips from GPS traces: each trace (a list of ``(lat, lon)`` fixes) is map-matched on
+    the provider's road graph (``GraphProvider.match``, routing/mapmatch.py) and becomes ``(node
+    path, observed seconds)`` when it matched in exactly one connected path with no unmatched fix.
+    Returns the trips and the indices of the traces dropped (unmatched fixes, a break, or a path of
+    fewer than two nodes, which carries nothing to learn from)."""
+    if len(traces) != len(observed_seconds):
+        raise ValueError("one observed duration per trace")
+    trips: List[Tuple[List[int], float]] = []
+    dropped: List[int] = []
+    for i, r in enumerate(provider.match(traces, ctx=ctx, params=params, device=device) if len(traces) else []):
+        whole = (r["n_segments"] == 1 and len(r["matchings"]) == 1 and bool((r["matched"] >= 0).all())
+                 and len(r["matchings"][0]["nodes"]) >= 2)
+        if whole:
+            trips.append(([int(v) for v in r["matchings"][0]["nodes"]], float(observed_seconds[i])))
+        else:
+            dropped.append(i)
+    return trips, dropped
 
 
 def predicted_hidden(delay: torch.Tensor, T: Dict[str, torch.Tensor], n_trips: int) -> torch.Tensor:

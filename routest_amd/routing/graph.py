@@ -672,6 +672,17 @@ class GraphProvider(HaversineProvider):
                             "reach_m": float(em[mask[eu] & mask[ev]].sum())})
         return out
 
+    def match(self, traces: Sequence[Any], ctx=None, params=None, device=None) -> List[Dict[str, Any]]:
+        """Map-match GPS traces (each a list of ``(lat, lon)`` fixes) to connected node paths under
+        the request's context: ``routing.mapmatch.match_traces`` on the CCH router of ``device``
+        (HIP kernels on a GPU, the host reference otherwise)."""
+        if self.engine == "astar":
+            raise ProviderError("map matching needs the CCH router: ROUTEST_ROUTER=astar has no batched pair "
+                                "metres under a context (unset it or use ROUTEST_ROUTER=cch)")
+        from .mapmatch import match_traces
+        with self.pinned_metric(ctx, device) as key:
+            return match_traces(self.router(device), self.g, traces, key, params)
+
     def directions(self, coords: List[List[float]], profile: str, ctx=None) -> Dict[str, Any]:
         nodes, pairs = self.leg_pairs(coords)
         with self.pinned_metric(ctx) as key:
