@@ -21,10 +21,19 @@
 //           they cannot overflow);
 // only searches that exceed max_iters fall back to the host.  Small batches (interactive flushes)
 // skip the lane tier: one 64-lane wave per search fills the chip.
-// Heuristic: max(great-circle distance x circuity / v_max, ALT landmark bound); edge costs are floored
-// at length / v_max on the host, so both are admissible and consistent (ALT tables are shrunk by 1e-4
-// against fp32 rounding).  Every search stops within max_iters pops (status 3), on overflow (2) or
-// when the open set empties (1): the grid always drains.
+// Heuristic: max(great-circle distance x inv_vmax, ALT landmark bound).  inv_vmax is the host's
+// great_circle_factor (routing/graph.py): the smallest cost per great-circle metre over the edges of
+// the graph and metric at hand — NOT a fixed circuity over a speed limit: lengths read from a file
+// bear no fixed ratio to the great circle.  The ALT tables hold a landmark's largest finite distance
+// where it has no route (one-way streets, islands), never infinity.  Both terms are then admissible
+// and consistent on any directed graph (the great-circle term is shrunk by 1e-3, the ALT bound by
+// 1e-4, against fp32 rounding); both tiers rely on that: the lane tier never reopens a closed node,
+// the wave tier stops when no open f is below g(t).  Every search stops within max_iters pops
+// (status 3), on overflow (2) or when the open set empties (1): the grid always drains.
+// Limit: the wave tier opens the band [fmin, fmin + delta) and moves entries with f < fmin + delta;
+// where fmin + delta == fmin in f32 (f above ~1.3e8 s at the default delta of 10) no entry would move
+// and the band loop would not end.  Costs and table entries must stay far below that — which is why
+// unreachable table entries are finite distances and no sentinel.
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -396,9 +405,12 @@ __global__ __launch_bounds__(64) void astar_kernel(AstarArgs a, const int* __res
 //
 // Label-correcting (a node is re-expanded when its g improves; stale duplicates are harmless), so
 // costs are exact.  The table is shared by the wave's lanes: a key is claimed with atomicCAS (the
-// claimer records the slot for the reset), the state word is lowered with atomicMin, and plain
-// loads only ever see older (larger) words, which at worst cost a redundant atomic.  The heap row
-// holds near A | near B | far.
+// claimer records the slot for the reset), the state word is lowered with atomicMin (across an edge
+// that adds nothing to g: only to a strictly smaller g, see the relaxation), and plain loads only
+// ever see older (larger) words, which at worst cost a redundant atomic.  The heap row holds
+// near A | near B | far.  The lists are sized for 8 pushes per expanded node; a node of larger
+// degree may push more, and every push is bounds-checked: the search then ends with status 2 and
+// is rerun in the next tier (or finished on the host).
 // (waves_per_eu 4: the compiler fits the kernel in 102 VGPRs instead of 136 with no scratch, so four
 // searches per SIMD are resident instead of three; the tier is bound by dependent-load latency)
 template <int K, int NW>
@@ -670,8 +682,29 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 8)))
               if (ti < tcap) touched[ti] = p;
               else s_bad = 1;                        // (the reset then clears the whole table)
             }
-            const unsigned long long old = atomicMin(&tab[p].w, nw);
-            if (nw >= old) continue;
+            if (__builtin_expect(ng > gv, 1)) {
+              // minimum over the packed (g, parent) word: at an equal g the smaller parent slot wins
+              const unsigned long long old = atomicMin(&tab[p].w, nw);
+              if (nw >= old) continue;
+            } else {
+              // ... which must not happen across a FLAT edge, one that adds nothing to g (cost 0, or
+              // a cost below half an ulp of g): two nodes joined by flat edges both ways would
+              // become each other's parent, write_path would never reach s and the route would be
+              // reported as status 4.  A flat edge lowers the word only to a STRICTLY smaller g:
+              // compare-and-swap from the word as loaded (a failed swap returns the current one).
+              // Parent pointers then cannot close a cycle: g(child) >= g(parent) always holds, a
+              // cycle's edges are all flat, and the relaxation closing it would have to lower
+              // g(v) strictly below the g of v's own descendant u while setting it to g(u).
+              unsigned long long old =
+                  __hip_atomic_load(&tab[p].w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              bool won = false;
+              while (ng < w_g(old)) {
+                const unsigned long long prev = atomicCAS(&tab[p].w, old, nw);
+                if (prev == old) { won = true; break; }
+                old = prev;
+              }
+              if (!won) continue;
+            }
             float hu = tab[p].h;
             if (hu != hu) {
               hu = heur(u);

@@ -126,13 +126,33 @@ def permute_csr(indptr: np.ndarray, indices: np.ndarray, perm: np.ndarray):
     return perm, inv, new_ptr, new_idx, edge_perm
 
 
-def landmark_tables(g: RoadGraph, cost: np.ndarray, k: int = 16, seed: int = 0,
-                    method: str = "sectors") -> np.ndarray:
-    """ALT preprocessing: K landmarks, forward d(L -> v) and backward d(v -> L) shortest-path
-    tables, interleaved per node as [N][2K] = (fwd_k, fwd_k+1, bwd_k, bwd_k+1) float4 groups
-    (csrc/astar.hip::halt).  ``sectors``: the outermost node of K angular sectors around the centre;
-    ``farthest``: greedy farthest-point selection in travel time (each new landmark maximises its
-    distance to the chosen set)."""
+def great_circle_factor(g: RoadGraph, cost: np.ndarray) -> float:
+    """Seconds per great-circle metre that no edge of (g, cost) beats: min over the edges of
+    cost_e / gc_e (gc_e = great-circle distance between the edge's end nodes, float64; edges between
+    coincident nodes do not constrain it), shrunk by 1e-4 and rounded down to an f32 value, which is
+    what the kernel receives.  h(v) = factor * gc(v, t) is then admissible (a path's cost is at least
+    factor times the sum of its edges' great-circle spans, which is at least gc(v, t)) and
+    consistent (the triangle inequality of the great circle) for ANY lengths and costs; on a graph
+    whose lengths are all 1.15 x great circle it is 1.15 / v_max.  0.0 when some edge costs nothing."""
+    src = np.repeat(np.arange(g.num_nodes), np.diff(g.indptr))
+    gc = haversine_m(g.lat[src], g.lon[src], g.lat[g.indices], g.lon[g.indices]).astype(np.float64)
+    pos = gc > 0
+    if not pos.any():
+        return 0.0
+    c = np.maximum(np.asarray(cost, dtype=np.float64)[pos], 0.0)
+    x = float((c / gc[pos]).min()) / 1.0001
+    f = np.float32(x)
+    if float(f) > x:
+        f = np.nextafter(f, np.float32(0.0))
+    return float(f)
+
+
+def landmark_distances(g: RoadGraph, cost: np.ndarray, k: int = 16, seed: int = 0,
+                       method: str = "sectors") -> Tuple[np.ndarray, np.ndarray]:
+    """K landmarks and their float64 shortest-path distances (fwd [K, N] = d(L_k -> v), bwd [K, N] =
+    d(v -> L_k); inf where there is no route).  ``sectors``: the outermost node of K angular sectors
+    around the centre; ``farthest``: greedy farthest-point selection in travel time (each new
+    landmark maximises its distance to the chosen set)."""
     from scipy.sparse import csr_matrix
     from scipy.sparse.csgraph import dijkstra
     m = csr_matrix((np.asarray(cost, dtype=np.float64), g.indices, g.indptr), shape=(g.num_nodes,) * 2)
@@ -155,16 +175,43 @@ def landmark_tables(g: RoadGraph, cost: np.ndarray, k: int = 16, seed: int = 0,
             lo, hi = -np.pi + 2 * np.pi * i / k, -np.pi + 2 * np.pi * (i + 1) / k
             sector = np.where((ang >= lo) & (ang < hi))[0]
             lms.append(int(sector[np.argmax(rad[sector])]) if len(sector) else int(np.argmax(rad)))
-    fwd = dijkstra(m, directed=True, indices=lms)
-    bwd = dijkstra(m.T.tocsr(), directed=True, indices=lms)
-    fwd = np.where(np.isfinite(fwd), fwd, 0.0).astype(np.float32)
-    bwd = np.where(np.isfinite(bwd), bwd, 0.0).astype(np.float32)
-    out = np.empty((g.num_nodes, k // 2, 4), dtype=np.float32)
+    return dijkstra(m, directed=True, indices=lms), dijkstra(m.T.tocsr(), directed=True, indices=lms)
+
+
+def interleave_tables(fwd: np.ndarray, bwd: np.ndarray) -> np.ndarray:
+    """[K, N] forward and backward tables -> [N][2K] f32, per node (fwd_k, fwd_k+1, bwd_k, bwd_k+1)
+    float4 groups (csrc/astar.hip::halt)."""
+    k, n = fwd.shape
+    out = np.empty((n, k // 2, 4), dtype=np.float32)
     out[:, :, 0] = fwd[0::2].T
     out[:, :, 1] = fwd[1::2].T
     out[:, :, 2] = bwd[0::2].T
     out[:, :, 3] = bwd[1::2].T
-    return out.reshape(g.num_nodes, 2 * k)
+    return out.reshape(n, 2 * k)
+
+
+def landmark_tables(g: RoadGraph, cost: np.ndarray, k: int = 16, seed: int = 0,
+                    method: str = "sectors") -> np.ndarray:
+    """ALT preprocessing: K landmarks, forward d(L -> v) and backward d(v -> L) shortest-path
+    tables, interleaved per node as [N][2K] = (fwd_k, fwd_k+1, bwd_k, bwd_k+1) float4 groups
+    (csrc/astar.hip::halt).  ``sectors``: the outermost node of K angular sectors around the centre;
+    ``farthest``: greedy farthest-point selection in travel time (each new landmark maximises its
+    distance to the chosen set).
+
+    Where a landmark has no route to a node (or the node none to the landmark: one-way streets,
+    islands) the table holds the landmark's LARGEST FINITE distance in that direction, M, instead of
+    infinity.  The bound d(L,t) - d(L,v) then stays admissible and consistent: with t unreachable
+    from L and v reachable it is M - d(L,v) >= 0, but then v has no route to t either (L -> v -> t
+    would be one); with v unreachable it is d(L,t) - M <= 0; and on an edge v -> u the stored values
+    still satisfy F(u) <= F(v) + c (u is reachable whenever v is, and F(u) <= M always).  The
+    backward tables mirror this.  (Not infinity or a huge sentinel: the wave tier's f-bands need
+    f + delta > f in f32.)"""
+    fwd, bwd = landmark_distances(g, cost, k, seed, method)
+
+    def finite(d):           # [K, N]: a landmark's largest finite distance where there is no route
+        fin = np.isfinite(d)
+        return np.where(fin, d, np.where(fin, d, 0.0).max(axis=1, keepdims=True)).astype(np.float32)
+    return interleave_tables(finite(fwd), finite(bwd))
 
 
 def median_edge_m(g: RoadGraph, sample: int = 1 << 16) -> float:
@@ -309,12 +356,12 @@ class BatchedAstar:
         self.wave_nw = 0
         self.retry_nw = 0
         self.last_stats = {}
-        # tightest admissible + consistent heuristic: every edge length is 1.15 x its great-circle
-        # length (so any path >= 1.15 x the great-circle s-t distance) and every edge is traversed
-        # no faster than the fastest edge of the graph
+        # great-circle term of the heuristic: seconds per great-circle metre that no edge of this
+        # graph and metric beats (great_circle_factor: admissible and consistent whatever the
+        # lengths are — files give their own; 1.15 / v_max on graphs built with 1.15 x great circle)
         cost_np = np.asarray(cost, dtype=np.float64)
         self.v_max = float((g.length_m / np.maximum(cost_np, 1e-6)).max()) * 1.0001
-        self.inv_vmax = 1.15 / self.v_max
+        self.inv_vmax = great_circle_factor(g, cost_np)
         self.landmark_method = landmark_method
         self.lm = (torch.from_numpy(self._nodes(landmark_tables(g, cost, landmarks,
                                                                 method=landmark_method))).to(d)
@@ -338,7 +385,7 @@ class BatchedAstar:
         self.cost.copy_(torch.from_numpy(self._edges(cost)))
         self._csr = None          # the host fallback's CSR was built from the old costs
         self.v_max = float((self.g.length_m / np.maximum(cost.astype(np.float64), 1e-6)).max()) * 1.0001
-        self.inv_vmax = 1.15 / self.v_max
+        self.inv_vmax = great_circle_factor(self.g, cost)
         if self.lm is not None:
             self.lm.copy_(torch.from_numpy(self._nodes(landmark_tables(
                 self.g, cost, self.lm.shape[1] // 2, method=self.landmark_method))))
@@ -408,7 +455,8 @@ class BatchedAstar:
         from scipy.sparse.csgraph import dijkstra
         if getattr(self, "_csr", None) is None:
             # the device-order graph (node ids as the kernel sees them)
-            self._csr = csr_matrix((self.cost.double().cpu().numpy(), self.indices.cpu().numpy(),
+            self._csr_cost32 = self.cost.cpu().numpy()
+            self._csr = csr_matrix((self._csr_cost32.astype(np.float64), self.indices.cpu().numpy(),
                                     self.indptr.cpu().numpy()), shape=(self.g.num_nodes,) * 2)
         qi = bad.cpu().numpy()
         ss, tt = s[bad].cpu().numpy(), t[bad].cpu().numpy()
@@ -428,7 +476,13 @@ class BatchedAstar:
                 continue
             path.reverse()
             out_path[int(q), :len(path)] = torch.tensor(path, dtype=torch.int32, device=out_path.device)
-            cost_h[j], len_h[j], st_h[j] = float(dist[row, tv]), len(path), 0
+            # the cost the kernels would report for this path: its f32 sum, source first
+            ip, ix, c32 = self._csr.indptr, self._csr.indices, self._csr_cost32
+            tot = np.float32(0.0)
+            for u, v in zip(path[:-1], path[1:]):
+                e = slice(ip[u], ip[u + 1])
+                tot = np.float32(tot + c32[e][ix[e] == v].min())
+            cost_h[j], len_h[j], st_h[j] = float(tot), len(path), 0
         out_cost[bad] = cost_h.to(out_cost.device)
         out_len[bad] = len_h.to(out_len.device)
         out_status[bad] = st_h.to(out_status.device)
