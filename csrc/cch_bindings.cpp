@@ -284,6 +284,30 @@ class PyCchGpu {
     return py::make_tuple(sec, met);
   }
 
+  // rectangular matrices: src int32 [R, SM] / dst int32 [R, DM] node ids, nsrc / ndst int32 [R] ->
+  // (sec, metres) [R, SM, DM]; meet: CchGpu::MEET_* (0: the default)
+  py::tuple matrix_rect(int64_t key, torch::Tensor src, torch::Tensor nsrc, torch::Tensor dst, torch::Tensor ndst,
+                        int64_t meet) {
+    auto m = get(key);
+    for (const torch::Tensor* t : {&src, &nsrc, &dst, &ndst})
+      TORCH_CHECK(t->is_cuda() && t->device().index() == dev_ && t->scalar_type() == torch::kInt32 && t->is_contiguous(),
+                  "src / nsrc / dst / ndst: int32 on the router's GPU");
+    TORCH_CHECK(src.dim() == 2 && dst.dim() == 2 && dst.size(0) == src.size(0) && nsrc.numel() == src.size(0) &&
+                    ndst.numel() == src.size(0),
+                "src [R, SM], dst [R, DM], nsrc [R], ndst [R]");
+    const int64_t R = src.size(0), SM = src.size(1), DM = dst.size(1);
+    TORCH_CHECK(R * (SM + DM) <= INT32_MAX && R * SM * DM <= INT32_MAX, "matrix_rect: too many chains or cells for one call");
+    // (counts outside 0..SM / 0..DM act as clamped: the kernels only compare slot indices with them)
+    auto of = torch::TensorOptions().dtype(torch::kFloat32).device(torch::kCUDA, dev_);
+    auto sec = torch::empty({R, SM, DM}, of), met = torch::empty({R, SM, DM}, of);
+    const c10::DeviceGuard guard(src.device());
+    std::lock_guard<std::mutex> lk(mu_);
+    CCH_CHECK_HIP(g_->matrix_rect(*m, src.data_ptr<int>(), nsrc.data_ptr<int>(), dst.data_ptr<int>(),
+                                  ndst.data_ptr<int>(), (int)R, (int)SM, (int)DM, sec.data_ptr<float>(),
+                                  met.data_ptr<float>(), *sc_, stream_of(dev_), (int)meet));
+    return py::make_tuple(sec, met);
+  }
+
   // matrix() that also returns the tag of its chains (kept for legs_from_matrix until the next call)
   py::tuple matrix_keep(int64_t key, torch::Tensor pts, torch::Tensor npts) {
     auto sm = matrix(key, pts, npts);
@@ -420,6 +444,8 @@ void bind_cch_gpu(py::module& m) {
       .def("route", &PyCchGpu::route, py::arg("key"), py::arg("src"), py::arg("dst"), py::arg("max_path") = 4096,
            py::arg("want_path") = true)
       .def("matrix", &PyCchGpu::matrix, py::arg("key"), py::arg("pts"), py::arg("npts"))
+      .def("matrix_rect", &PyCchGpu::matrix_rect, py::arg("key"), py::arg("src"), py::arg("nsrc"), py::arg("dst"),
+           py::arg("ndst"), py::arg("meet") = 0)
       .def("matrix_keep", &PyCchGpu::matrix_keep, py::arg("key"), py::arg("pts"), py::arg("npts"))
       .def("legs_from_matrix", &PyCchGpu::legs_from_matrix, py::arg("key"), py::arg("tag"), py::arg("pts"), py::arg("r"),
            py::arg("i"), py::arg("j"), py::arg("max_path") = 4096, py::arg("want_path") = true)

@@ -244,6 +244,18 @@ class CchGpu {
   hipError_t legs_from_matrix(const CchMetricDev& m, const int* d_src, const int* d_r, const int* d_i, const int* d_j,
                               int Q, uint64_t tag, const CchRouteOut& o, CchScratch& sc, hipStream_t s);
   static constexpr int MAX_ARCS = 1024;   // shortcut arcs per path before unpacking
+  // rectangular many-to-many per row: src [R][SM] / dst [R][DM] node ids (nsrc[r] / ndst[r] used, 0
+  // allowed) -> seconds and metres [R][SM][DM] (f32, both required): one forward chain per source,
+  // one backward chain per destination, then every cell's meet.  Equal nodes and cells past nsrc /
+  // ndst are 0, unreachable ones +inf.  Overwrites the scratch's chains (a matrix() tag dies);
+  // hipErrorInvalidValue when R (SM + DM) or R SM DM does not fit an int.  meet: MEET_RECT, the tile
+  // kernel (a workgroup per source and 64 destinations; needs 12 bytes of LDS per chain depth);
+  // MEET_PAIRS, meet_kernel over the same cells (bit-identical); MEET_AUTO, the tile kernel where its
+  // LDS fits; MEET_NONE, jobs and sweeps only, outputs untouched (benches: the meet's share).
+  enum { MEET_AUTO = 0, MEET_RECT = 1, MEET_PAIRS = 2, MEET_NONE = 3 };
+  hipError_t matrix_rect(const CchMetricDev& m, const int* d_src, const int* d_nsrc, const int* d_dst,
+                         const int* d_ndst, int R, int SM, int DM, float* d_sec, float* d_met, CchScratch& sc,
+                         hipStream_t s, int meet = MEET_AUTO);
 
   // one-to-all (csrc/cch_all.hip; CPU reference rcch::one_to_all, bit-identical): d_src [S] node ids
   // on the device -> d_sec / d_met [S][N] by node id, +inf where unreachable; reverse: all-to-one,

@@ -9,6 +9,8 @@
 // deepest tie) and lists the shortcut arcs of the chosen up-down path; the unpack kernels expand them
 // to road nodes (cooperatively, 16 lanes per pair; a serial DFS per lane for the longest arc lists).
 // Many-to-many matrices reuse each point's two chains, and legs can reuse a matrix call's chains.
+// Rectangular matrices sweep one forward chain per source and one backward chain per destination
+// and meet per (source, tile of 64 destinations) with the source's chain in LDS (meet_rect_kernel).
 #include "cch_dev.h"
 #include "cch_gpu.h"
 
@@ -542,6 +544,171 @@ __global__ void matrix_out_kernel(const int* __restrict__ npts, int R, int NM, f
   if (D64) D64[g] = (double)m;
 }
 
+// rectangular matrix: jobs [R][SM + DM] — row r's forward chains of its sources, then the backward
+// chains of its destinations; a padding slot is -1 (no chain is swept)
+__global__ void rect_jobs_kernel(const int* __restrict__ src, const int* __restrict__ nsrc, const int* __restrict__ dst,
+                                 const int* __restrict__ ndst, int R, int SM, int DM, const int32_t* __restrict__ rank,
+                                 int N, int32_t* __restrict__ jobs) {
+  const long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  const int W = SM + DM;
+  if (g >= (long long)R * W) return;
+  const int r = (int)(g / W), k = (int)(g % W);
+  const bool fwd = k < SM;
+  const int i = fwd ? k : k - SM;
+  if (i >= (fwd ? nsrc[r] : ndst[r])) {
+    jobs[g] = -1;
+    return;
+  }
+  int v = fwd ? src[(size_t)r * SM + i] : dst[(size_t)r * DM + i];
+  if (v < 0 || v >= N) v = 0;
+  jobs[g] = (rank[v] << 1) | (fwd ? 0 : 1);
+}
+
+// One workgroup per (row, source, tile of MEET_TILE destinations) of a rectangular matrix.  The
+// source's forward chain (node ranks, labels, predecessor arcs of depths 0..ds) is staged in LDS
+// once; the waves then take the tile's destinations in turn and do meet_kernel's search (other
+// root: unreachable; LCA depth by binary search; min of F[d] + B[d] over the common depths, deepest
+// tie) with the source side read from LDS; after a barrier lane p sums pair p's metres in
+// meet_kernel's order (forward arcs from the meeting depth down to s, then backward ones down to t,
+// f32 from 0.f), the tile's walks side by side instead of one lane per wave.  The output rule is
+// fused: equal nodes and cells past nsrc / ndst are 0, unreachable ones +inf.
+constexpr int MEET_TILE = 64;
+constexpr int MEET_THREADS = 256;
+__global__ __launch_bounds__(MEET_THREADS) void meet_rect_kernel(
+    int SM, int DM, const int* __restrict__ nsrc, const int* __restrict__ ndst, const int32_t* __restrict__ jobs,
+    int stride, const float* __restrict__ sdist, const int32_t* __restrict__ spred, const int32_t* __restrict__ snode,
+    const int32_t* __restrict__ depth, const int32_t* __restrict__ arc_lo, const float* __restrict__ len_up,
+    const float* __restrict__ len_dn, float* __restrict__ out_sec, float* __restrict__ out_met) {
+  extern __shared__ unsigned char smem[];
+  int32_t* fn = reinterpret_cast<int32_t*>(smem);
+  float* fd = reinterpret_cast<float*>(smem + (size_t)stride * 4);
+  int32_t* fp = reinterpret_cast<int32_t*>(smem + (size_t)stride * 8);
+  __shared__ float s_best[MEET_TILE];
+  __shared__ int s_bestd[MEET_TILE];
+  const int tid = threadIdx.x;
+  const int ntile = (DM + MEET_TILE - 1) / MEET_TILE;
+  const int tile = blockIdx.x % ntile;
+  const int i = (blockIdx.x / ntile) % SM;
+  const int r = blockIdx.x / (ntile * SM);
+  const int j0 = tile * MEET_TILE;
+  const int nj = min(MEET_TILE, DM - j0);                     // cells of the tile
+  const int nv = min(nj, ndst[r] - j0);                       // of which real destinations (may be <= 0)
+  const size_t cell = ((size_t)r * SM + i) * DM + j0;
+  if (i >= nsrc[r] || nv <= 0) {                              // padding only (uniform in the workgroup)
+    if (tid < nj) {
+      out_sec[cell + tid] = 0.f;
+      out_met[cell + tid] = 0.f;
+    }
+    return;
+  }
+  const size_t jrow = (size_t)r * (SM + DM);
+  const int s = jobs[jrow + i] >> 1;
+  const int ds = depth[s];
+  const size_t bf = (jrow + i) * stride;
+  for (int d = tid; d <= ds; d += MEET_THREADS) {
+    fn[d] = snode[bf + d];
+    fd[d] = sdist[bf + d];
+    fp[d] = spred[bf + d];
+  }
+  __syncthreads();
+  const int lane = tid & 63;
+  for (int p = tid >> 6; p < nv; p += MEET_THREADS / 64) {
+    const size_t jb = jrow + SM + j0 + p;
+    const int t = jobs[jb] >> 1;
+    const int dt = depth[t];
+    const size_t bb = jb * stride;
+    float best = F_INF;
+    int bestd = -1;
+    if (fn[0] == snode[bb]) {
+      // chains agree on depths [0, L]
+      int lo = 0, hi = ds < dt ? ds : dt;
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (fn[mid] == snode[bb + mid]) lo = mid;
+        else hi = mid - 1;
+      }
+      const int L = lo;
+      for (int d = lane; d <= L; d += 64) {
+        const float v = fd[d] + sdist[bb + d];
+        if (v < best || (v == best && d > bestd)) {
+          best = v;
+          bestd = d;
+        }
+      }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        const float ov = __shfl_xor(best, o);
+        const int od = __shfl_xor(bestd, o);
+        if (ov < best || (ov == best && od > bestd)) {
+          best = ov;
+          bestd = od;
+        }
+      }
+    }
+    if (lane == 0) {
+      s_best[p] = best;
+      s_bestd[p] = bestd;
+    }
+  }
+  __syncthreads();
+  if (tid >= nj) return;
+  float sec = 0.f, met = 0.f;
+  if (tid < nv) {
+    const size_t jb = jrow + SM + j0 + tid;
+    const int t = jobs[jb] >> 1;
+    if (t != s) {
+      sec = s_best[tid];
+      if (sec < F_INF) {
+        const int dt = depth[t];
+        const size_t bb = jb * stride;
+        const int bestd = s_bestd[tid];
+        for (int slot = bestd; slot != ds;) {
+          const int a = fp[slot];
+          met += len_up[a];
+          slot = depth[arc_lo[a]];
+        }
+        for (int slot = bestd; slot != dt;) {
+          const int a = spred[bb + slot];
+          met += len_dn[a];
+          slot = depth[arc_lo[a]];
+        }
+      } else {
+        sec = met = F_INF;
+      }
+    }
+  }
+  out_sec[cell + tid] = sec;
+  out_met[cell + tid] = met;
+}
+
+// The same cells through meet_kernel (one wave per pair): pair job indices and the output rule
+__global__ void rect_pairs_kernel(int R, int SM, int DM, int32_t* __restrict__ pjf, int32_t* __restrict__ pjb) {
+  const long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (g >= (long long)R * SM * DM) return;
+  const int r = (int)(g / ((long long)SM * DM));
+  const int rem = (int)(g % ((long long)SM * DM));
+  pjf[g] = r * (SM + DM) + rem / DM;
+  pjb[g] = r * (SM + DM) + SM + rem % DM;
+}
+
+__global__ void rect_out_kernel(const int* __restrict__ nsrc, const int* __restrict__ ndst, int R, int SM, int DM,
+                                const int32_t* __restrict__ jobs, float* __restrict__ sec, float* __restrict__ met) {
+  const long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (g >= (long long)R * SM * DM) return;
+  const int r = (int)(g / ((long long)SM * DM));
+  const int rem = (int)(g % ((long long)SM * DM));
+  const int i = rem / DM, j = rem % DM;
+  float s = sec[g], m = met[g];
+  const size_t jrow = (size_t)r * (SM + DM);
+  if (i >= nsrc[r] || j >= ndst[r] || (jobs[jrow + i] >> 1) == (jobs[jrow + SM + j] >> 1)) s = m = 0.f;
+  else {
+    if (s < 0.f) s = F_INF;
+    if (m < 0.f) m = F_INF;
+  }
+  sec[g] = s;
+  met[g] = m;
+}
+
 }  // namespace
 
 CchScratch::~CchScratch() {
@@ -686,6 +853,46 @@ hipError_t CchGpu::matrix_multi(const CchMView* d_mv, const int* d_row_grp, cons
                                 int NM, float* d_sec, float* d_met, double* d_D64, CchScratch& sc, hipStream_t s) {
   if (d_mv == nullptr || d_row_grp == nullptr) return hipErrorInvalidValue;
   return matrix_impl(nullptr, d_mv, d_row_grp, d_pts, d_npts, R, NM, d_sec, d_met, d_D64, sc, s);
+}
+
+hipError_t CchGpu::matrix_rect(const CchMetricDev& m, const int* d_src, const int* d_nsrc, const int* d_dst,
+                               const int* d_ndst, int R, int SM, int DM, float* d_sec, float* d_met, CchScratch& sc,
+                               hipStream_t s, int meet) {
+  if (R <= 0 || SM <= 0 || DM <= 0) return hipSuccess;
+  if (d_sec == nullptr || d_met == nullptr || meet < MEET_AUTO || meet > MEET_NONE) return hipErrorInvalidValue;
+  const int S = stride();
+  const size_t J = (size_t)R * ((size_t)SM + DM), P = (size_t)R * SM * DM;
+  if (J > (size_t)INT32_MAX || P > (size_t)INT32_MAX) return hipErrorInvalidValue;
+  const size_t lds = (size_t)S * 12;
+  const bool fits = lds + MEET_TILE * 8 <= 64 * 1024;          // else the chains do not fit one workgroup's LDS
+  if (meet == MEET_RECT && !fits) return hipErrorInvalidValue;
+  if (meet == MEET_AUTO) meet = fits ? MEET_RECT : MEET_PAIRS;
+  sc.device = dev_;
+  sc.chain_tag = 0;                                            // a kept matrix's chains are overwritten
+  // (MEET_PAIRS: the pair job indices live in the arcs buffer, 2 ints per pair)
+  hipError_t e = sc.ensure(J, meet == MEET_PAIRS ? (P * 2 + MAX_ARCS - 1) / MAX_ARCS + 1 : 0, S, MAX_ARCS);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(rect_jobs_kernel, dim3(blocks_for((long long)J, 256)), dim3(256), 0, s, d_src, d_nsrc, d_dst,
+                     d_ndst, R, SM, DM, d_rank, T_.N, sc.jobs);
+  hipLaunchKernelGGL(sweep_kernel, dim3((unsigned)J), dim3(64), (size_t)S * 8, s, sc.jobs, (int)J, d_parent, d_depth,
+                     T_.N, m.f_ptr, m.f_rec, m.b_ptr, m.b_rec, S, sc.dist, sc.pred, sc.node, nullptr, nullptr, 1);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (meet == MEET_RECT) {
+    const size_t blocks = (size_t)R * SM * ((DM + MEET_TILE - 1) / MEET_TILE);
+    hipLaunchKernelGGL(meet_rect_kernel, dim3((unsigned)blocks), dim3(MEET_THREADS), lds, s, SM, DM, d_nsrc, d_ndst,
+                       sc.jobs, S, sc.dist, sc.pred, sc.node, d_depth, d_arc_lo, m.len_up, m.len_dn, d_sec, d_met);
+  } else if (meet == MEET_PAIRS) {
+    int32_t* pjf = sc.arcs;
+    int32_t* pjb = sc.arcs + P;
+    hipLaunchKernelGGL(rect_pairs_kernel, dim3(blocks_for((long long)P, 256)), dim3(256), 0, s, R, SM, DM, pjf, pjb);
+    hipLaunchKernelGGL(meet_kernel, dim3((unsigned)P), dim3(64), 0, s, (int)P, pjf, pjb, 0, 0, sc.jobs, S, sc.dist,
+                       sc.pred, sc.node, d_depth, d_arc_lo, m.len_up, m.len_dn, d_sec, d_met, nullptr, nullptr, nullptr,
+                       MAX_ARCS, nullptr, nullptr, 1);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(rect_out_kernel, dim3(blocks_for((long long)P, 256)), dim3(256), 0, s, d_nsrc, d_ndst, R, SM, DM,
+                       sc.jobs, d_sec, d_met);
+  }
+  return hipGetLastError();
 }
 
 hipError_t CchGpu::legs_impl(const CchMetricDev* m, const CchMView* mv, const int* grp, const int* d_src,

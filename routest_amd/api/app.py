@@ -522,6 +522,27 @@ def create_app(services: Optional[Services] = None, settings: Optional[Settings]
             return JSONResponse({"error": str(e)}, 400)
         return JSONResponse(res, 200)
 
+    @app.post("/api/matrix")
+    async def matrix(request: Request):
+        """Durations and / or distances from ``sources`` to ``destinations`` among ``locations``
+        under the request's context (ORS's matrix shape; routing/matrix.py): one rectangular
+        many-to-many call of the CCH router, ``null`` where there is no route."""
+        body = await _json_body(request, silent=False)
+        if isinstance(body, Response):
+            return body
+        if getattr(sv.provider, "name", "") != "graph" or not hasattr(sv.provider, "matrix_rect"):
+            return JSONResponse({"error": "matrices need the road graph: start the service with "
+                                          "ROUTEST_PROVIDER=graph"}, 400)
+        from ..routing.cch import RouteContext
+        from ..routing.matrix import matrix_response
+        from ..routing.providers import ProviderError
+        try:
+            res = await run_in_threadpool(matrix_response, sv.provider, body, RouteContext.from_request(body),
+                                          sv.route_device)
+        except (ValueError, ProviderError) as e:
+            return JSONResponse({"error": str(e)}, 400)
+        return JSONResponse(res, 200)
+
     @app.post("/api/match")
     async def match(request: Request):
         """Map-match GPS traces to the road graph under the request's context (OSRM's match shape

@@ -11,8 +11,8 @@ cached").
 * :class:`RouteContext` — the context of one request (the dashboard sends ``weather: "Sunny",
   traffic: "Medium"``; defaults ``Sunny`` / ``Low`` like the reference's ETA; week-hour of
   ``context.pickup_time`` when it is an ISO string, else of now, local time).
-* :class:`RoadRouter` — legs and many-to-many matrices under a context.  GPU: ``_C.CchGpu``
-  (csrc/cch.hip: costs, customization and queries all on the device, LRU of customized contexts in
+* :class:`RoadRouter` — legs, square and rectangular many-to-many matrices under a context.
+  GPU: ``_C.CchGpu`` (csrc/cch.hip: costs, customization and queries all on the device, LRU of customized contexts in
   HBM).  CPU: ``_rt.CCH`` (csrc/runtime/cch.h, the bit-identical reference, multi-threaded).
 
 Legs come back as (seconds, metres, status, node path); a matrix entry is the metre length of the
@@ -38,6 +38,19 @@ from ..utils.timeutil import parse_iso
 #: city-wide traffic level of a request -> congestion shift of every edge's level (graph.py
 #: edge_traffic); a missing or unknown level is the reference's default, "Low"
 CONGESTION = {"Low": 0, "Medium": 1, "High": 2, "Jam": 3}
+
+
+RECT_MAX_CELLS = 1 << 27      # cells of one rectangular-matrix call (two f32 outputs: 1 GiB)
+RECT_CPU_PAIRS = 1 << 20      # pair queries of one call of the CPU router's rectangular matrices
+
+
+def _rect_max_jobs(max_jobs: Optional[int]) -> int:
+    if max_jobs is None:
+        from .mapmatch import PAIR_CHUNK
+        return 2 * PAIR_CHUNK
+    if isinstance(max_jobs, bool) or int(max_jobs) < 1:
+        raise ValueError("max_jobs: a positive integer")
+    return int(max_jobs)
 
 
 @dataclass(frozen=True)
@@ -274,6 +287,118 @@ class RoadRouter:
         np.fill_diagonal(sec, 0.0)
         np.fill_diagonal(met, 0.0)
         return sec, met
+
+    # ---- rectangular matrices ----
+    def matrix_rect(self, sources: Sequence[int], destinations: Sequence[int], ctx_or_key,
+                    max_jobs: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(seconds, metres) f32 [S, D] from every source to every destination: S forward and D
+        backward chain sweeps and S x D meets (csrc/cch_query.hip meet_rect_kernel), where the
+        square :meth:`matrix` of the union would sweep 2 (S + D) chains and meet (S + D)² pairs.
+        Unreachable cells are inf, a cell whose two nodes are equal is 0.  Metres are those of the
+        time-shortest path with :meth:`route`'s tie rule (the deepest meeting node of minimum
+        seconds), not :meth:`one_to_all`'s shorter-path rule: a cell equals the leg's bits."""
+        return self.matrices_rect([(sources, destinations)], ctx_or_key, max_jobs=max_jobs)[0]
+
+    def matrices_rect(self, pairs_of_lists: Sequence[Tuple[Sequence[int], Sequence[int]]], ctx_or_key,
+                      max_jobs: Optional[int] = None) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """:meth:`matrix_rect` of many (sources, destinations) rows, ragged rows packed into padded
+        calls.  One call sweeps at most ``max_jobs`` chains (default ``2 * mapmatch.PAIR_CHUNK``,
+        what a pair-query call of the matcher sweeps, so the scratch's high-water mark is the
+        same): consecutive rows share a call while their padded chains and cells fit, a single row
+        above ``max_jobs`` is split along its destinations (and, if its sources alone exceed it,
+        along them too — a call never sweeps less than one source and one destination)."""
+        rows = []
+        N = self.g.num_nodes
+        for s, d in pairs_of_lists:
+            s = np.ascontiguousarray(s, dtype=np.int32).reshape(-1)
+            d = np.ascontiguousarray(d, dtype=np.int32).reshape(-1)
+            for a in (s, d):
+                if len(a) and (a.min() < 0 or a.max() >= N):
+                    raise IndexError("node id out of range")
+            rows.append((s, d))
+        mj = _rect_max_jobs(max_jobs)
+        out: List[Any] = [None] * len(rows)
+        with self.pinned(ctx_or_key) as key:
+            lo = 0
+            while lo < len(rows):
+                # rows lo..hi of one padded call
+                sm, dm, hi = len(rows[lo][0]), len(rows[lo][1]), lo + 1
+                while hi < len(rows):
+                    s2, d2 = max(sm, len(rows[hi][0])), max(dm, len(rows[hi][1]))
+                    n = hi - lo + 1
+                    if n * (s2 + d2) > mj or n * s2 * d2 > RECT_MAX_CELLS:
+                        break
+                    sm, dm, hi = s2, d2, hi + 1
+                n = hi - lo
+                src = np.zeros((n, sm), dtype=np.int32)
+                dst = np.zeros((n, dm), dtype=np.int32)
+                nsrc = np.zeros(n, dtype=np.int32)
+                ndst = np.zeros(n, dtype=np.int32)
+                for r, (s, d) in enumerate(rows[lo:hi]):
+                    src[r, :len(s)], dst[r, :len(d)] = s, d
+                    nsrc[r], ndst[r] = len(s), len(d)
+                sec, met = self.rect_rows(*(torch.from_numpy(a).to(self.dev) for a in (src, nsrc, dst, ndst)), key, mj)
+                sec, met = sec.cpu().numpy(), met.cpu().numpy()
+                for r, (s, d) in enumerate(rows[lo:hi]):
+                    out[lo + r] = (sec[r, :len(s), :len(d)].copy(), met[r, :len(s), :len(d)].copy())
+                lo = hi
+        return out
+
+    def rect_rows(self, src: torch.Tensor, nsrc: torch.Tensor, dst: torch.Tensor, ndst: torch.Tensor, key: int,
+                  max_jobs: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The padded form under an already customized metric ``key``, tensors on the router's
+        device in and out: ``src`` int32 [R, SM], ``dst`` int32 [R, DM] (valid node ids in every
+        slot), ``nsrc`` / ``ndst`` int32 [R] -> (seconds, metres) f32 [R, SM, DM] with cells past a
+        row's counts 0.  Chunked as :meth:`matrices_rect` describes (rows first, then columns)."""
+        mj = _rect_max_jobs(max_jobs)
+        R, SM, DM = int(src.shape[0]), int(src.shape[1]), int(dst.shape[1])
+        sec = torch.zeros((R, SM, DM), dtype=torch.float32, device=src.device)
+        met = torch.zeros((R, SM, DM), dtype=torch.float32, device=src.device)
+        if R == 0 or SM == 0 or DM == 0:
+            return sec, met
+        sp, dp = SM, DM
+        if SM + DM > mj:
+            sp = SM if SM < mj else max(1, mj // 2)
+            dp = max(1, min(DM, mj - sp))
+        sp = min(sp, RECT_MAX_CELLS)
+        dp = max(1, min(dp, RECT_MAX_CELLS // sp))
+        rows = max(1, min(mj // (sp + dp), RECT_MAX_CELLS // (sp * dp)))
+        call = self._rect_call_gpu if self.gpu is not None else self._rect_call_cpu
+        if sp == SM and dp == DM and rows >= R:
+            return call(src.contiguous(), nsrc.contiguous(), dst.contiguous(), ndst.contiguous(), key)
+        for s0 in range(0, SM, sp):
+            s1 = min(SM, s0 + sp)
+            for d0 in range(0, DM, dp):
+                d1 = min(DM, d0 + dp)
+                for r0 in range(0, R, rows):
+                    r1 = min(R, r0 + rows)
+                    a, b = call(src[r0:r1, s0:s1].contiguous(), (nsrc[r0:r1] - s0).clamp(0, s1 - s0).contiguous(),
+                                dst[r0:r1, d0:d1].contiguous(), (ndst[r0:r1] - d0).clamp(0, d1 - d0).contiguous(), key)
+                    sec[r0:r1, s0:s1, d0:d1] = a
+                    met[r0:r1, s0:s1, d0:d1] = b
+        return sec, met
+
+    def _rect_call_gpu(self, src, nsrc, dst, ndst, key: int):
+        return tuple(self.gpu.matrix_rect(key, src, nsrc, dst, ndst))
+
+    def _rect_call_cpu(self, src, nsrc, dst, ndst, key: int):
+        """The reference: ``_rt.CCH.query`` over the rows' real cells, with the output rule."""
+        src, nsrc, dst, ndst = (np.asarray(a.numpy()) for a in (src, nsrc, dst, ndst))
+        R, SM, DM = src.shape[0], src.shape[1], dst.shape[1]
+        sec = np.zeros((R, SM, DM), dtype=np.float32)
+        met = np.zeros((R, SM, DM), dtype=np.float32)
+        real = (np.arange(SM)[None, :, None] < nsrc[:, None, None]) & (np.arange(DM)[None, None, :] < ndst[:, None, None])
+        r, i, j = np.nonzero(real)
+        s, t = src[r, i], dst[r, j]
+        for lo in range(0, len(r), RECT_CPU_PAIRS):
+            sl = slice(lo, lo + RECT_CPU_PAIRS)
+            a, m, st, _ = self.cpu.query(self._cpu_metrics[key], np.ascontiguousarray(s[sl]),
+                                         np.ascontiguousarray(t[sl]), False, self.max_path)
+            found = (np.asarray(st) == 0) | (np.asarray(st) == 4)       # 4: a route whose listing would be refused
+            same = s[sl] == t[sl]
+            sec[r[sl], i[sl], j[sl]] = np.where(same, np.float32(0), np.where(found, np.asarray(a), np.float32(np.inf)))
+            met[r[sl], i[sl], j[sl]] = np.where(same, np.float32(0), np.where(found, np.asarray(m), np.float32(np.inf)))
+        return torch.from_numpy(sec), torch.from_numpy(met)
 
     def one_to_all(self, sources: Sequence[int], ctx_or_key, reverse: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """(seconds, metres) [S, N] from every source to every node id (``reverse``: from every

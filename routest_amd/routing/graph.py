@@ -681,6 +681,25 @@ class GraphProvider(HaversineProvider):
             _, met = self.router().matrix(list(map(int, nodes)), key)
         return met.astype(np.float64)
 
+    def matrix_rect(self, points: List[Dict[str, float]], sources: Sequence[int], destinations: Sequence[int],
+                    ctx=None, device=None):
+        """Rectangular road matrix between snapped points (``POST /api/matrix``): ``sources`` /
+        ``destinations`` index ``points``.  Returns (seconds f32 [S, D], metres f32 [S, D] of the
+        time-shortest paths, inf where there is no route; the snapped node of every point; every
+        point's snap distance in metres) from ONE ``RoadRouter.matrix_rect`` call under the
+        request's context."""
+        if self.engine == "astar":
+            raise ProviderError("matrices by sources and destinations need the CCH router: ROUTEST_ROUTER=astar "
+                                "has no rectangular many-to-many search (unset it or use ROUTEST_ROUTER=cch)")
+        from .providers import haversine_scalar
+        nodes = np.asarray(self.g.nearest_nodes([p["lat"] for p in points], [p["lon"] for p in points]), dtype=np.int32)
+        snap = np.array([haversine_scalar(p["lat"], p["lon"], float(self.g.lat[n]), float(self.g.lon[n]))
+                         for p, n in zip(points, nodes)], dtype=np.float64)
+        with self.pinned_metric(ctx, device) as key:
+            sec, met = self.router(device).matrix_rect(nodes[np.asarray(sources, dtype=np.int64)],
+                                                       nodes[np.asarray(destinations, dtype=np.int64)], key)
+        return sec, met, nodes, snap
+
     def _street_edges(self):
         """(tail, head, metres) of every street once: a two-way street's two directed edges count
         as one (the lower -> higher node id one), a one-way street's only edge as itself."""

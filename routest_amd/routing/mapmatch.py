@@ -16,7 +16,9 @@ previous kept fix to the next kept one.
 **Costs** over the kept fixes ``t``: ``emit(t, j) = beta_cm * cand_d2[t][j]``;
 ``g(t) = isqrt(d2(fix[t-1], fix[t]))``; ``r(t, i, j)`` is 0 for equal nodes, else the centimetres
 (``llrint(float64(metres_f32) * 100)``) of the time-shortest road path between the two candidates
-under the request's routing context (``RoadRouter.route``; feasible on status 0 and 4);
+under the request's routing context (``RoadRouter.route``; feasible on status 0 and 4; asked as
+deduplicated pair queries or, ``transitions="matrix"``, as one rectangular matrix row per step —
+the same bits either way);
 ``trans(t, i, j) = 2 * sigma_cm² * |r - g(t)|``, infeasible without a route or with
 ``|r - g(t)| > max_detour_cm``.
 
@@ -46,6 +48,10 @@ MAX_POINTS = 2048          # fixes of one trace
 MAX_K = 16
 MAX_TRACES = 64            # traces of one POST /api/match
 PAIR_CHUNK = 1 << 22       # pair queries of one router call
+RECT_MAX_JOBS = 2 * PAIR_CHUNK   # chains of one rectangular-matrix call (what PAIR_CHUNK pairs sweep)
+#: what transitions="auto" asks a GPU router for: the matrix rows measured faster than the pair
+#: queries on the 1,000 x 100 workload (profiles/cch_matrix_rect.md, part c)
+AUTO_TRANSITIONS_GPU = "matrix"
 LEG_CHUNK = 1 << 15        # legs with node listings of one router call
 MAX_SPAN_CM = 2_000_000_000   # a trace's extent per axis: keeps d2 between its fixes below 2^63
 DEAD = 1 << 62             # score of a dead state (above any path score, see MatchParams)
@@ -365,7 +371,8 @@ def _as_latlon(trace) -> np.ndarray:
 
 
 def match_traces(router, g: RoadGraph, traces: Sequence[Any], ctx_or_key, params: Optional[MatchParams] = None,
-                 device=None, stats: Optional[Dict[str, Any]] = None) -> List[Dict[str, Any]]:
+                 device=None, stats: Optional[Dict[str, Any]] = None,
+                 transitions: str = "auto") -> List[Dict[str, Any]]:
     """Match GPS traces (each a list of ``(lat, lon)`` fixes) to the road graph.
 
     ``router``: a :class:`routing.cch.RoadRouter` (its device decides where the matcher runs: HIP
@@ -375,10 +382,21 @@ def match_traces(router, g: RoadGraph, traces: Sequence[Any], ctx_or_key, params
     fix, -1 unmatched), ``cand_d2`` (cm² from the fix to its node, -1 unmatched), ``n_segments`` and
     ``matchings``: per stitched path ``{"segment", "nodes" (int32), "duration", "distance"}``.
     ``stats``: a dict that receives the seconds of each stage (the device is synchronized around
-    them, so only pass it to measure) and the number of pair queries."""
+    them, so only pass it to measure) and the number of pair queries.
+
+    ``transitions``: how the steps' candidate-to-candidate road metres are asked.  ``"pairs"``: the
+    unique (src, dst) pairs of all steps as pair queries, two chain sweeps each.  ``"matrix"``: one
+    rectangular matrix row per step (``RoadRouter.rect_rows``: previous fix's candidates x this
+    fix's), 2K sweeps per step instead of up to 2K², no pair table (``pairs_queried`` then counts
+    the cells asked).  ``"auto"``: :data:`AUTO_TRANSITIONS_GPU` on a GPU router, ``"pairs"`` on
+    the CPU router.  All three return ``==`` results."""
     import time
     params = params or MatchParams()
     dev = router.dev
+    if transitions not in ("auto", "pairs", "matrix"):
+        raise ValueError("transitions: 'auto', 'pairs' or 'matrix'")
+    if transitions == "auto":
+        transitions = AUTO_TRANSITIONS_GPU if router.gpu is not None else "pairs"
 
     def lap(name: str) -> None:
         if stats is not None:
@@ -434,21 +452,37 @@ def match_traces(router, g: RoadGraph, traces: Sequence[Any], ctx_or_key, params
         step = torch.arange(1, T, device=dev)[None, :] < npts[:, None]             # [B, T-1] steps that exist
         dy, dx = Qy[:, 1:] - Qy[:, :-1], Qx[:, 1:] - Qx[:, :-1]
         gg = torch.where(step, _isqrt_t(dy * dy + dx * dx), torch.zeros_like(dy))
-        # the unique (src, dst) pairs of all steps of all traces, self pairs dropped
-        src = Cn[:, :-1, :, None].long().expand(B, T - 1, K, K)
-        dst = Cn[:, 1:, None, :].long().expand(B, T - 1, K, K)
-        valid = step[:, :, None, None] & (src >= 0) & (dst >= 0)
-        R = torch.where(valid & (src == dst), 0, -1).to(torch.int64)
-        ask = (valid & (src != dst)).nonzero(as_tuple=True)
         n_pairs = 0
-        if ask[0].numel():
-            N = int(g.num_nodes)
-            uniq, inv = torch.unique(src[ask] * N + dst[ask], return_inverse=True)
-            n_pairs = int(uniq.numel())
-            lap("pairs_build_s")
-            cm = _route_cm(router, key, uniq // N, uniq % N)
-            lap("pair_queries_s")
-            R[ask] = cm[inv]
+        if transitions == "matrix":
+            # one rectangular row per step that exists: candidates of t-1 x candidates of t
+            R = torch.full((B, T - 1, K, K), -1, dtype=torch.int64, device=dev)
+            rows = step.flatten().nonzero().flatten()
+            if rows.numel():
+                cs = Cn[:, :-1].reshape(-1, K)[rows].contiguous()
+                cd = Cn[:, 1:].reshape(-1, K)[rows].contiguous()
+                ns, nd = (cs >= 0).sum(1).to(torch.int32), (cd >= 0).sum(1).to(torch.int32)    # -1 pads the tail
+                n_pairs = int((ns.long() * nd.long()).sum().item())
+                lap("pairs_build_s")
+                _, met = router.rect_rows(cs.clamp(min=0), ns, cd.clamp(min=0), nd, key, RECT_MAX_JOBS)
+                lap("pair_queries_s")
+                cm = torch.round(met.double() * 100.0).long()
+                real = (cs >= 0)[:, :, None] & (cd >= 0)[:, None, :] & torch.isfinite(met)
+                R.view(-1, K, K)[rows] = torch.where(real, cm, torch.full_like(cm, -1))
+        else:
+            # the unique (src, dst) pairs of all steps of all traces, self pairs dropped
+            src = Cn[:, :-1, :, None].long().expand(B, T - 1, K, K)
+            dst = Cn[:, 1:, None, :].long().expand(B, T - 1, K, K)
+            valid = step[:, :, None, None] & (src >= 0) & (dst >= 0)
+            R = torch.where(valid & (src == dst), 0, -1).to(torch.int64)
+            ask = (valid & (src != dst)).nonzero(as_tuple=True)
+            if ask[0].numel():
+                N = int(g.num_nodes)
+                uniq, inv = torch.unique(src[ask] * N + dst[ask], return_inverse=True)
+                n_pairs = int(uniq.numel())
+                lap("pairs_build_s")
+                cm = _route_cm(router, key, uniq // N, uniq % N)
+                lap("pair_queries_s")
+                R[ask] = cm[inv]
         R, gg, npts32 = R.contiguous(), gg.contiguous(), npts.to(torch.int32)
         lap("pairs_build_s")
         choice, seg, nseg, _ = run_viterbi(Cd, Nc, R, gg, npts32, params)
