@@ -131,6 +131,7 @@ CchGpu::~CchGpu() {
   dfree(d_bofs);
   dfree(d_pofs);
   free_tables();
+  free_geometry();
   free_scratch(cs0_);
   (void)hipSetDevice(cur);
 }
@@ -174,7 +175,34 @@ void CchGpu::insert_cached(const std::shared_ptr<CchMetricDev>& m) {
   std::lock_guard<std::mutex> lk(mu_);
   if (cache_gb_ > 0.0 && b > 0) capacity_ = (int)std::max<int64_t>(4, (int64_t)(cache_gb_ * 1073741824.0 / (double)b));
   cache_.push_front(m);
+  // metrics with avoid areas share a quarter of the slots: a client that sends a new polygon with
+  // every request evicts its own metrics, not the week-hour contexts everyone uses
+  if (m->avoid) {
+    const int cap = std::max(1, capacity_ / 4);
+    int n = 0;
+    for (const auto& x : cache_) n += x->avoid != nullptr;
+    for (auto it = cache_.end(); n > cap && it != cache_.begin();) {
+      --it;
+      if ((*it)->avoid) {
+        it = cache_.erase(it);
+        --n;
+      }
+    }
+  }
   while ((int)cache_.size() > capacity_) cache_.pop_back();
+}
+
+static bool same_avoid(const std::shared_ptr<const std::vector<int32_t>>& a,
+                       const std::shared_ptr<const std::vector<int32_t>>& b) {
+  return a == b || (a && b && *a == *b);
+}
+
+bool CchGpu::avoid_clash(const CchContext& c) {
+  const uint64_t key = c.key();
+  std::lock_guard<std::mutex> lk(mu_);
+  for (const auto& m : cache_)
+    if (m->key == key) return !same_avoid(m->avoid, c.avoid);
+  return false;
 }
 
 void CchGpu::set_cache_gb(double gb) {
@@ -189,7 +217,7 @@ void CchGpu::request_build(const CchContext& c, bool urgent) {
   const uint64_t key = c.key();
   std::shared_ptr<CchMetricDev> m;
   if (cached_metric(key, m)) {
-    notify_built(key, true);
+    notify_built(key, same_avoid(m->avoid, c.avoid));
     return;
   }
   {
@@ -346,13 +374,19 @@ hipError_t CchGpu::metric_for(const CchContext& c, hipStream_t s, std::shared_pt
   const uint64_t key = c.key();
   if (fresh) *fresh = false;
   auto lookup = [&]() -> bool { return cached_metric(key, out); };
-  if (lookup()) return hipSuccess;
+  // the key under another avoid set (equal digests): never that set's metric
+  auto checked = [&]() -> hipError_t {
+    if (same_avoid(out->avoid, c.avoid)) return hipSuccess;
+    out.reset();
+    return hipErrorInvalidValue;
+  };
+  if (lookup()) return checked();
   {
     // a context another caller is building: wait for it, then hit; different contexts build
     // concurrently (each caller on its own stream and temporaries)
     std::unique_lock<std::mutex> lk(mu_inflight_);
     cv_inflight_.wait(lk, [&] { return inflight_.count(key) == 0; });
-    if (lookup()) return hipSuccess;
+    if (lookup()) return checked();
     inflight_.insert(key);
   }
   struct Done {
@@ -369,6 +403,7 @@ hipError_t CchGpu::metric_for(const CchContext& c, hipStream_t s, std::shared_pt
   auto m = std::make_shared<CchMetricDev>();
   m->key = key;
   m->device = dev_;
+  m->avoid = c.avoid;
   const auto ta = std::chrono::steady_clock::now();
   hipError_t e = dmalloc(m->cost, T_.E);
   m->alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();

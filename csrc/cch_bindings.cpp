@@ -6,6 +6,7 @@
 #include <c10/core/DeviceGuard.h>
 
 #include <chrono>
+#include <cmath>
 #include <memory>
 #include <mutex>
 #include <unordered_map>
@@ -59,6 +60,52 @@ class PyCchGpu {
                                       host_ptr<uint8_t>(base_traffic, E, "base_traffic"), dev_);
     sc_ = std::make_unique<rt::CchScratch>();
     asc_ = std::make_unique<rt::CchAllScratch>();
+    // avoid areas work on microdegrees: q(x) = rint(x * 1e6), round-half-even (routing/avoid.py)
+    std::vector<int32_t> qx((size_t)N), qy((size_t)N);
+    const double* la = lat.data_ptr<double>();
+    const double* lo = lon.data_ptr<double>();
+    for (int64_t v = 0; v < N; ++v) {
+      TORCH_CHECK(std::fabs(la[v]) <= 90.0 && std::fabs(lo[v]) <= 180.0, "node coordinate out of range");
+      qx[v] = (int32_t)std::nearbyint(lo[v] * 1e6);
+      qy[v] = (int32_t)std::nearbyint(la[v] * 1e6);
+    }
+    g_->set_geometry(ip, ix, qx.data(), qy.data());
+  }
+
+  // a context from its fields; avoid: the canonical int32 blob (CPU tensor) of routing/avoid.py
+  rt::CchContext context(int64_t weather, int64_t congestion, int64_t weekhour, double age,
+                         const c10::optional<torch::Tensor>& avoid, int64_t digest) const {
+    rt::CchContext c;
+    c.weather = (int)weather;
+    c.congestion = (int)congestion;
+    c.weekhour = (int)weekhour;
+    c.driver_age = (float)age;
+    if (avoid.has_value()) {
+      c.avoid = blob_of(*avoid);
+      TORCH_CHECK(digest > 0 && digest < ((int64_t)1 << 31), "avoid_digest: 1 .. 2^31 - 1");
+      c.avoid_digest = (uint32_t)digest;
+    }
+    return c;
+  }
+  static std::shared_ptr<const std::vector<int32_t>> blob_of(const torch::Tensor& t) {
+    TORCH_CHECK(!t.is_cuda() && t.scalar_type() == torch::kInt32 && t.dim() == 1 && t.is_contiguous(),
+                "avoid: int32 [n] CPU tensor");
+    return std::make_shared<const std::vector<int32_t>>(t.data_ptr<int32_t>(), t.data_ptr<int32_t>() + t.numel());
+  }
+
+  // uint8 [E] on the router's GPU: 1 where the avoid set closes the edge (tests, benches)
+  torch::Tensor avoid_mask(torch::Tensor blob) {
+    auto b = blob_of(blob);
+    auto out = torch::empty({(int64_t)g_->topo().E}, torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA, dev_));
+    const c10::DeviceGuard guard(out.device());
+    hipError_t e;
+    {
+      py::gil_scoped_release nogil;
+      e = g_->avoid_mask(*b, out.data_ptr<uint8_t>(), stream_of(dev_));
+    }
+    if (e == hipErrorInvalidValue) throw py::value_error("avoid: not a valid avoid-set blob");
+    CCH_CHECK_HIP(e);
+    return out;
   }
 
   void set_eta(torch::Tensor blob, int64_t H, std::vector<double> norm, int64_t variant) {
@@ -115,13 +162,10 @@ class PyCchGpu {
   }
 
   // queue a context's build on the router's background builder (returns at once)
-  void request_build(int64_t weather, int64_t congestion, int64_t weekhour, double age, bool urgent) {
+  void request_build(int64_t weather, int64_t congestion, int64_t weekhour, double age, bool urgent,
+                     c10::optional<torch::Tensor> avoid, int64_t avoid_digest) {
     TORCH_CHECK(g_->has_eta(), "CchGpu: set_eta first");
-    rt::CchContext c;
-    c.weather = (int)weather;
-    c.congestion = (int)congestion;
-    c.weekhour = (int)weekhour;
-    c.driver_age = (float)age;
+    const rt::CchContext c = context(weather, congestion, weekhour, age, avoid, avoid_digest);
     g_->request_build(c, urgent);
   }
   bool is_cached(int64_t key) {
@@ -150,13 +194,10 @@ class PyCchGpu {
   // metric of a routing context (built on first use, then cached on the GPU).  pin: also hold it
   // outside the LRU until unpin(key) — a caller that customizes several contexts and then queries
   // them (a flush with more contexts than the cache holds) cannot lose one to eviction in between
-  py::dict metric_for(int64_t weather, int64_t congestion, int64_t weekhour, double age, bool pin) {
+  py::dict metric_for(int64_t weather, int64_t congestion, int64_t weekhour, double age, bool pin,
+                      c10::optional<torch::Tensor> avoid, int64_t avoid_digest) {
     TORCH_CHECK(g_->has_eta(), "CchGpu: set_eta first");
-    rt::CchContext c;
-    c.weather = (int)weather;
-    c.congestion = (int)congestion;
-    c.weekhour = (int)weekhour;
-    c.driver_age = (float)age;
+    const rt::CchContext c = context(weather, congestion, weekhour, age, avoid, avoid_digest);
     const c10::DeviceGuard guard(c10::Device(c10::DeviceType::CUDA, dev_));
     std::shared_ptr<rt::CchMetricDev> m;
     bool fresh = false;
@@ -165,6 +206,10 @@ class PyCchGpu {
       py::gil_scoped_release nogil;
       e = g_->metric_for(c, stream_of(dev_), m, &fresh);
     }
+    if (e == hipErrorInvalidValue && g_->avoid_clash(c))
+      throw py::value_error("avoid set: its digest is cached for a different set (a 2^-31 collision); "
+                            "change a vertex by a microdegree or retry once that metric is evicted");
+    if (e == hipErrorInvalidValue && c.avoid) throw py::value_error("avoid: not a valid avoid-set blob");
     CCH_CHECK_HIP(e);
     if (pin) pin_ptr(m);
     return info(*m, fresh);
@@ -186,8 +231,8 @@ class PyCchGpu {
                 "cost: float32 [E] on the router's GPU");
     // weights are ordered by their float bits (cch.h pack_w, atomicMin on the bits): NaN, negative
     // costs and -0.0 would sort above every real weight and drop the edge — reject / normalise
-    TORCH_CHECK(torch::isfinite(cost).all().item<bool>() && (cost >= 0).all().item<bool>(),
-                "edge costs must be finite and >= 0");
+    // (+inf: the edge is absent from the metric; `cost >= 0` is false for NaN)
+    TORCH_CHECK((cost >= 0).all().item<bool>(), "edge costs must be >= 0 (+inf: edge absent), not NaN");
     cost = cost.add(0.0);                       // -0.0 -> +0.0
     const c10::DeviceGuard guard(cost.device());
     std::shared_ptr<rt::CchMetricDev> m;
@@ -435,7 +480,9 @@ void bind_cch_gpu(py::module& m) {
       .def("set_eta", &PyCchGpu::set_eta, py::arg("blob"), py::arg("H"), py::arg("norm"), py::arg("variant") = -1)
       .def("stats", &PyCchGpu::stats)
       .def("metric_for", &PyCchGpu::metric_for, py::arg("weather"), py::arg("congestion"), py::arg("weekhour"),
-           py::arg("driver_age") = 35.0, py::arg("pin") = false)
+           py::arg("driver_age") = 35.0, py::arg("pin") = false, py::arg("avoid") = py::none(),
+           py::arg("avoid_digest") = 0)
+      .def("avoid_mask", &PyCchGpu::avoid_mask, py::arg("blob"))
       .def("unpin", &PyCchGpu::unpin, py::arg("key"))
       .def("pinned", &PyCchGpu::pinned)
       .def("metric_from_costs", &PyCchGpu::metric_from_costs, py::arg("key"), py::arg("cost"))
@@ -457,7 +504,8 @@ void bind_cch_gpu(py::module& m) {
       .def("set_unpack_serial", &PyCchGpu::set_unpack_serial, py::arg("on"))
       .def("unpack_serial", &PyCchGpu::unpack_serial)
       .def("request_build", &PyCchGpu::request_build, py::arg("weather"), py::arg("congestion"), py::arg("weekhour"),
-           py::arg("driver_age") = 35.0, py::arg("urgent") = true)
+           py::arg("driver_age") = 35.0, py::arg("urgent") = true, py::arg("avoid") = py::none(),
+           py::arg("avoid_digest") = 0)
       .def("is_cached", &PyCchGpu::is_cached, py::arg("key"))
       .def("ptr", &PyCchGpu::ptr)
       .def("topology_arrays", &PyCchGpu::topology_arrays);

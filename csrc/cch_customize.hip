@@ -72,8 +72,9 @@ __global__ void edge_scatter_kernel(const float* __restrict__ cost, const int32_
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E) return;
   const int a = edge_arc[e];
-  if (a < 0) return;
-  atomicMin(edge_dir[e] ? dn + a : up + a, packw(cost[e], EDGE_FLAG_D | (uint32_t)e));
+  const float c = cost[e];
+  if (a < 0 || c == INFINITY) return;           // a self loop; an edge this metric closes (absent)
+  atomicMin(edge_dir[e] ? dn + a : up + a, packw(c, EDGE_FLAG_D | (uint32_t)e));
 }
 
 struct LevelArgs {
@@ -1699,6 +1700,9 @@ void CchGpu::free_scratch(CustScratch& x) {
   if (x.h_stage) (void)hipHostFree(x.h_stage);
   x.h_stage = nullptr;
   dfree(x.sup_buf);
+  dfree(x.avoid_dev);
+  if (x.avoid_host) (void)hipHostFree(x.avoid_host);
+  x.avoid_host = nullptr;
 }
 
 hipError_t CchGpu::context_costs(const CchContext& c, float* d_cost, hipStream_t s, CustScratch* cs) {
@@ -1721,6 +1725,8 @@ hipError_t CchGpu::context_costs(const CchContext& c, float* d_cost, hipStream_t
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(ctx_cost_kernel, dim3(blocks_for(E, 256)), dim3(256), 0, s, min_buf, d_length, d_class, E, d_cost);
   e = hipGetLastError();
+  // the context's avoid areas: +inf into the closed edges' costs (csrc/cch_avoid.hip)
+  if (e == hipSuccess && c.avoid) e = apply_avoid(*c.avoid, d_cost, nullptr, s, X);
   // the shared temporaries are free again only once this stream has consumed them
   if (e == hipSuccess && cs == nullptr) e = hipStreamSynchronize(s);
   return e;

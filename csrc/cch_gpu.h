@@ -28,11 +28,18 @@ namespace rt {
 // (routing/graph.py edge_records).  weather: features.py weather code (0..3, 255 unknown);
 // congestion: city-wide traffic level 0..3 (Low, Medium, High, Jam) shifting every edge's level;
 // weekhour: 0 = Monday 00:00 .. 167.
+// avoid: the areas this context closes (routing/avoid.py: the canonical int32 blob; shared, since
+// contexts are copied into the builders' queue) with the caller's 31-bit digest of it, which takes
+// bits 32..62 of the key.  Two sets may share a digest (2^-31 per pair): a metric remembers its
+// blob, and a lookup that finds the key under another blob fails instead of serving that metric.
 struct CchContext {
   int weather = 2, congestion = 1, weekhour = 9;
   float driver_age = 35.f;
+  std::shared_ptr<const std::vector<int32_t>> avoid;
+  uint32_t avoid_digest = 0;
   uint64_t key() const {
-    return (uint64_t)(weather & 0xFF) | ((uint64_t)(congestion & 0xFF) << 8) | ((uint64_t)(weekhour & 0xFFFF) << 16);
+    return (uint64_t)(weather & 0xFF) | ((uint64_t)(congestion & 0xFF) << 8) | ((uint64_t)(weekhour & 0xFFFF) << 16) |
+           (avoid ? (uint64_t)(avoid_digest & 0x7FFFFFFFu) << 32 : 0);
   }
 };
 
@@ -56,6 +63,7 @@ struct CchMetricDev {
   double basic_ms = 0.0, perfect_ms = 0.0, prune_ms = 0.0;   // device time per phase
   double alloc_ms = 0.0, hostcopy_ms = 0.0;                    // its device allocations; the host copy
   std::vector<float> host_cost;    // [E] the costs on the host (filled by customize before publishing)
+  std::shared_ptr<const std::vector<int32_t>> avoid;   // the avoid set it was built with (null: none)
   ~CchMetricDev();
 };
 
@@ -104,6 +112,8 @@ struct CustScratch {
   float* min_buf = nullptr;                        // their minutes [2E]
   float* h_stage = nullptr;                        // pinned [E]: the costs' host copy lands here first
   unsigned long long* sup_buf = nullptr;           // dense fronts of one supernode level (build_supernodes)
+  int32_t* avoid_dev = nullptr;                    // an avoid set's device words (csrc/cch_avoid.hip; lazy)
+  int32_t* avoid_host = nullptr;                   // pinned: where they are put together
 };
 
 // The device pointers of one metric that the query kernels read — an array of these plus a group
@@ -164,6 +174,15 @@ class CchGpu {
   bool has_eta() const { return eta_blob_ != nullptr; }
   // edge costs (s) of a context into d_cost [E] on the device (routing/graph.py edge_costs)
   hipError_t context_costs(const CchContext& c, float* d_cost, hipStream_t s, CustScratch* cs = nullptr);
+
+  // Avoid areas (csrc/cch_avoid.hip).  set_geometry: the graph's CSR and its nodes' quantized
+  // microdegrees, kept on the host; they go to the device with the first avoid set, so a router
+  // that never sees one allocates nothing there.  avoid_mask: d_mask [E] = 1 where the set closes
+  // the edge.  context_costs writes +inf into the costs of a context's closed edges.
+  void set_geometry(const int32_t* indptr, const int32_t* indices, const int32_t* qx, const int32_t* qy);
+  hipError_t avoid_mask(const std::vector<int32_t>& blob, uint8_t* d_mask, hipStream_t s);
+  // the context's key is cached under another avoid set (a digest collision)
+  bool avoid_clash(const CchContext& c);
 
   // customize m from d_cost ([E] on this device; copied into m.cost)
   hipError_t customize(const float* d_cost, CchMetricDev& m, hipStream_t s, CustScratch* cs = nullptr);
@@ -383,6 +402,13 @@ class CchGpu {
   double cache_gb_ = 48.0;
   std::atomic<int64_t> metric_bytes_{0};
   void insert_cached(const std::shared_ptr<CchMetricDev>& m);   // LRU push_front + eviction
+  // avoid areas: host geometry, its lazy device copy
+  hipError_t ensure_geometry();
+  void free_geometry();
+  hipError_t apply_avoid(const std::vector<int32_t>& blob, float* d_cost, uint8_t* d_mask, hipStream_t s, CustScratch& X);
+  std::mutex mu_geom_;
+  std::vector<int32_t> h_esrc_, h_edst_, h_qx_, h_qy_;
+  int32_t *d_esrc = nullptr, *d_edst = nullptr, *d_qx = nullptr, *d_qy = nullptr;
   std::atomic<uint64_t> tag_ctr_{0};
   // asynchronous builds
   void builder_loop(int idx);

@@ -643,7 +643,7 @@ class Reactor {
       c.async = true;
       ++inflight_;
       st_.route_requests.fetch_add(1, std::memory_order_relaxed);
-      if (!cfg_.routes->submit(j)) {             // the service is stopping: the app answers
+      if (!cfg_.routes->submit(j)) {             // stopping, or a request it leaves to the app: the app answers
         j->fallback = true;
         job_done(j);
       }

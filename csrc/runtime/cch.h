@@ -469,7 +469,7 @@ inline void customize(const Topology& T, const float* cost, const float* length,
   m.dn.assign(M, PACK_INF);
   for (int64_t e = 0; e < T.E; ++e) {
     const int32_t a = T.edge_arc[e];
-    if (a < 0) continue;
+    if (a < 0 || cost[e] == INF) continue;       // a self loop; an edge this metric closes
     const uint64_t p = pack_w(cost[e], EDGE_FLAG | (uint32_t)e);
     uint64_t& slot = T.edge_dir[e] ? m.dn[a] : m.up[a];
     if (p < slot) slot = p;

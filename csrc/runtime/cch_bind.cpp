@@ -10,6 +10,7 @@
 #include <vector>
 #include <memory>
 
+#include "avoid.h"
 #include "cch.h"
 
 namespace py = pybind11;
@@ -86,12 +87,14 @@ class PyCCH {
     return d;
   }
 
-  PyMetric customize(arr<float> cost, arr<float> length) {
+  PyMetric customize(arr<float> cost, arr<float> length, bool allow_inf) {
     if (cost.shape(0) != T_.E || length.shape(0) != T_.E) throw std::invalid_argument("cost/length per edge");
     // weights are ordered by their float bits (cch.h pack_w): a NaN, a negative cost or -0.0 (sign
     // bit set) would sort above every real weight and silently drop the edge — reject / normalise
     std::vector<float> c(cost.data(), cost.data() + T_.E);
     for (float& x : c) {
+      // allow_inf: +inf means the edge is absent from this metric (rcch::customize skips it)
+      if (allow_inf && x == rcch::INF) continue;
       if (!std::isfinite(x) || x < 0.f) throw std::invalid_argument("edge costs must be finite and >= 0");
       x += 0.f;                                 // -0.0 -> +0.0
     }
@@ -223,16 +226,40 @@ class PyCCH {
   double build_ms_ = 0.0;
 };
 
+
+// uint8 [E]: edges closed by an avoid set (avoid.h; qx / qy: quantized node longitudes / latitudes)
+py::array_t<uint8_t> avoid_mask_py(arr<int32_t> indptr, arr<int32_t> indices, arr<int32_t> qx, arr<int32_t> qy,
+                                   arr<int32_t> blob) {
+  const py::ssize_t N = qx.shape(0);
+  if (indptr.ndim() != 1 || indptr.shape(0) != N + 1 || qy.shape(0) != N || indptr.data()[0] != 0)
+    throw std::invalid_argument("graph shapes");
+  const int32_t* ip = indptr.data();
+  for (py::ssize_t v = 0; v < N; ++v)
+    if (ip[v] > ip[v + 1]) throw std::invalid_argument("indptr not monotone");
+  if (ip[N] != indices.shape(0)) throw std::invalid_argument("indices length");
+  for (py::ssize_t e = 0; e < indices.shape(0); ++e)
+    if (indices.data()[e] < 0 || indices.data()[e] >= N) throw std::out_of_range("edge target out of range");
+  py::array_t<uint8_t> mask(indices.shape(0));
+  {
+    py::gil_scoped_release nogil;
+    rtr::avoid_mask((int)N, ip, indices.data(), qx.data(), qy.data(), blob.data(), (int64_t)blob.shape(0),
+                    mask.mutable_data());
+  }
+  return mask;
+}
+
 }  // namespace
 
 void bind_cch(py::module& m) {
+  m.def("avoid_mask", &avoid_mask_py, py::arg("indptr"), py::arg("indices"), py::arg("qx"), py::arg("qy"),
+        py::arg("blob"));
   py::class_<PyMetric>(m, "CchMetric").def_readonly("customize_ms", &PyMetric::ms);
   py::class_<PyCCH>(m, "CCH")
       .def(py::init<arr<int32_t>, arr<int32_t>, arr<double>, arr<double>, unsigned>(), py::arg("indptr"),
            py::arg("indices"), py::arg("lat"), py::arg("lon"), py::arg("threads") = 0)
       .def("stats", &PyCCH::stats)
       .def("arrays", &PyCCH::arrays)
-      .def("customize", &PyCCH::customize, py::arg("cost"), py::arg("length"))
+      .def("customize", &PyCCH::customize, py::arg("cost"), py::arg("length"), py::arg("allow_inf") = false)
       .def("query", &PyCCH::query, py::arg("metric"), py::arg("src"), py::arg("dst"), py::arg("want_path") = true,
            py::arg("max_path") = 1 << 20)
       .def("one_to_all", &PyCCH::one_to_all, py::arg("metric"), py::arg("sources"), py::arg("reverse") = false)

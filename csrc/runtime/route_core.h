@@ -259,6 +259,7 @@ struct Pt {
 
 struct RouteReq {
   bool fallback = false;          // hand to the Python app
+  bool avoid = false;             // ... because it carries options.avoid_polygons
   std::string error;              // optimize_route's {"error": ...} (set instead of a route)
   const Value* root = nullptr;
   Pt src;
@@ -312,6 +313,9 @@ inline RouteReq parse_route_request(const Value* root) {
   }
   const Value* drv = root->get("driver_details");
   if (drv && drv->truthy() && drv->kind != Value::Obj) { r.fallback = true; return r; }
+  // avoid areas (routing/avoid.py) re-weight the road graph per request: the app answers those
+  const Value* opt = root->get("options");
+  if (opt && opt->kind == Value::Obj && opt->get("avoid_polygons")) { r.fallback = r.avoid = true; return r; }
   // candidate routes ranked by the GCN scorer (routing/alternatives.py): a number >= 2 asks for
   // them (bools and strings do not: app.py _route); the route service answers them with the graph
   // provider once the scorer is ready, else the app does

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "alternatives.h"
+#include "avoid.h"
 #include "history_db.h"
 #include "map_match.h"
 #include "route_core.h"
@@ -515,6 +516,75 @@ static void fuzz_mm_viterbi(std::mt19937_64& rng, int iters) {
   }
 }
 
+// avoid.h: the mask is symmetric in edge direction, an edge with an endpoint on a polygon vertex is
+// closed, a far-away set closes nothing; damaged blobs are refused (never read out of bounds)
+static void fuzz_avoid_mask(std::mt19937_64& rng, int iters) {
+  for (int it = 0; it < iters / 20; ++it) {
+    const int N = 2 + (int)(rng() % 40);
+    std::vector<int32_t> qx(N), qy(N);
+    for (int i = 0; i < N; ++i) {
+      qx[i] = 121000000 + (int32_t)(rng() % 13) - 6;
+      qy[i] = 14500000 + (int32_t)(rng() % 13) - 6;
+    }
+    // CSR with both directions of every undirected edge (and a self loop now and then)
+    std::vector<std::vector<int32_t>> adj(N);
+    const int und = 1 + (int)(rng() % (2 * N));
+    for (int k = 0; k < und; ++k) {
+      const int u = (int)(rng() % N), v = (int)(rng() % N);
+      adj[u].push_back(v);
+      if (u != v) adj[v].push_back(u);
+    }
+    std::vector<int32_t> indptr(N + 1, 0), indices;
+    for (int u = 0; u < N; ++u) {
+      for (int32_t v : adj[u]) indices.push_back(v);
+      indptr[u + 1] = (int32_t)indices.size();
+    }
+    const int P = 1 + (int)(rng() % 3);
+    std::vector<int32_t> nring(P), nvert, xy;
+    for (int p = 0; p < P; ++p) {
+      nring[p] = 1 + (int32_t)(rng() % 2);
+      for (int r = 0; r < nring[p]; ++r) {
+        const int nv = 3 + (int)(rng() % 4);
+        nvert.push_back(nv);
+        for (int i = 0; i < nv; ++i) {
+          xy.push_back(121000000 + (int32_t)(rng() % 13) - 6);
+          xy.push_back(14500000 + (int32_t)(rng() % 13) - 6);
+        }
+      }
+    }
+    std::vector<int32_t> blob{P, (int32_t)nvert.size(), (int32_t)(xy.size() / 2)};
+    blob.insert(blob.end(), nring.begin(), nring.end());
+    blob.insert(blob.end(), nvert.begin(), nvert.end());
+    blob.insert(blob.end(), xy.begin(), xy.end());
+    std::vector<uint8_t> mask(indices.size(), 2);
+    rtr::avoid_mask(N, indptr.data(), indices.data(), qx.data(), qy.data(), blob.data(), (int64_t)blob.size(), mask.data());
+    for (int u = 0; u < N; ++u)
+      for (int32_t e = indptr[u]; e < indptr[u + 1]; ++e) {
+        const int32_t v = indices[e];
+        CHECK(mask[e] <= 1, "avoid_mask: edge %d not written", e);
+        for (int32_t f = indptr[v]; f < indptr[v + 1]; ++f)
+          if (indices[f] == u) CHECK(mask[f] == mask[e], "avoid_mask: %d->%d and back differ", u, v);
+        bool on_vertex = false;
+        for (size_t i = 0; i + 1 < xy.size(); i += 2)
+          on_vertex |= (xy[i] == qx[u] && xy[i + 1] == qy[u]) || (xy[i] == qx[v] && xy[i + 1] == qy[v]);
+        if (on_vertex) CHECK(mask[e] == 1, "avoid_mask: edge %d touches a vertex and is open", e);
+      }
+    // the same set moved away closes nothing
+    std::vector<int32_t> far(blob);
+    for (size_t i = 3 + (size_t)P + nvert.size(); i < far.size(); i += 2) far[i] += 1000;
+    rtr::avoid_mask(N, indptr.data(), indices.data(), qx.data(), qy.data(), far.data(), (int64_t)far.size(), mask.data());
+    for (size_t e = 0; e < mask.size(); ++e) CHECK(mask[e] == 0, "avoid_mask: far set closes edge %zu", e);
+    // damage: one word changed, or cut short — parsed within bounds or refused
+    std::vector<int32_t> bad(blob);
+    if (rng() % 2) bad[rng() % (3 + (size_t)P + nvert.size())] = (int32_t)(rng() % 4096) - 8;
+    else bad.resize(rng() % bad.size());
+    try {
+      rtr::avoid_mask(N, indptr.data(), indices.data(), qx.data(), qy.data(), bad.data(), (int64_t)bad.size(), mask.data());
+    } catch (const std::invalid_argument&) {
+    }
+  }
+}
+
 // alternatives.h: via nodes stay in range, unique, within the detour band, and reproducible; the
 // argmin treats non-finite scores as +inf
 static void fuzz_alternatives(std::mt19937_64& rng, int iters) {
@@ -802,6 +872,7 @@ int main(int argc, char** argv) {
   fuzz_history(rng, iters);
   fuzz_mm_candidates(rng, iters);
   fuzz_mm_viterbi(rng, iters);
+  fuzz_avoid_mask(rng, iters);
   store_while_reading();
   threaded_pack_format(20000);
   std::printf("rt_selftest: %d iterations, %d failures\n", iters, g_fail);

@@ -150,10 +150,20 @@ def optimize_with_alternatives(payload: Dict[str, Any], provider, scorer, search
     ctx = None
     if getattr(provider, "uses_context", False):
         from .cch import RouteContext
-        ctx = RouteContext.from_request(payload)      # resolved once: planning and assembly agree
+        try:
+            ctx = RouteContext.from_request(payload)  # resolved once: planning and assembly agree
+        except ValueError as e:                       # a malformed options.avoid_polygons
+            return {"error": str(e)}
+    elif isinstance(payload.get("options"), dict) and payload["options"].get("avoid_polygons") is not None:
+        return optimize_route(payload, provider, engine)       # its 400
     if hasattr(provider, "pinned_metric"):
-        with provider.pinned_metric(ctx) as key:      # the metric stays usable for the whole request
-            return _alternatives_on(payload, provider, scorer, search, engine, k, ctx, key)
+        try:
+            with provider.pinned_metric(ctx) as key:  # the metric stays usable for the whole request
+                return _alternatives_on(payload, provider, scorer, search, engine, k, ctx, key)
+        except ValueError as e:
+            if ctx is None or ctx.avoid is None:
+                raise
+            return {"error": str(e)}
     return _alternatives_on(payload, provider, scorer, search, engine, k, ctx, None)
 
 

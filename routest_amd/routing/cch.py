@@ -34,6 +34,7 @@ import torch
 from ..data.graph import RoadGraph
 from ..models.features import weather_code
 from ..utils.timeutil import parse_iso
+from .avoid import AvoidSet, avoid_mask, parse_options
 
 #: city-wide traffic level of a request -> congestion shift of every edge's level (graph.py
 #: edge_traffic); a missing or unknown level is the reference's default, "Low"
@@ -59,10 +60,12 @@ class RouteContext:
     congestion: int = 0       # 0..3
     weekhour: int = 9         # Monday 00:00 = 0
     driver_age: float = 35.0  # the edge-cost model's fixed driver (a route does not depend on who drives)
+    avoid: Optional[AvoidSet] = None   # areas closed to this request (options.avoid_polygons)
 
     @property
     def key(self) -> int:
-        return (self.weather & 0xFF) | ((self.congestion & 0xFF) << 8) | ((self.weekhour & 0xFFFF) << 16)
+        k = (self.weather & 0xFF) | ((self.congestion & 0xFF) << 8) | ((self.weekhour & 0xFFFF) << 16)
+        return k if self.avoid is None else k | ((self.avoid.digest & 0x7FFFFFFF) << 32)
 
     @classmethod
     def from_request(cls, data: Any, now: Optional[dt.datetime] = None) -> "RouteContext":
@@ -82,7 +85,7 @@ class RouteContext:
             pickup = now or dt.datetime.now()
         return cls(weather=weather_code(w) if isinstance(w, str) else 255,
                    congestion=CONGESTION.get(t, 0) if isinstance(t, str) else 0,
-                   weekhour=pickup.weekday() * 24 + pickup.hour)
+                   weekhour=pickup.weekday() * 24 + pickup.hour, avoid=parse_options(data))
 
 
 def base_traffic(g: RoadGraph) -> np.ndarray:
@@ -100,6 +103,13 @@ def context_costs_cpu(g: RoadGraph, eta_model, ctx: RouteContext) -> np.ndarray:
     weather = {0: "Cloudy", 1: "Stormy", 2: "Sunny", 3: "Windy"}.get(ctx.weather, "Unknown")
     return edge_costs(g, eta_model, None, weather=weather, congestion=ctx.congestion, pickup=pickup,
                       driver_age=ctx.driver_age)
+
+
+def _avoid_args(ctx: RouteContext) -> tuple:
+    """The (blob tensor, digest) arguments ``_C.CchGpu`` takes for a context's avoid set."""
+    if ctx.avoid is None:
+        return None, 0
+    return torch.from_numpy(ctx.avoid.array.astype(np.int32)), int(ctx.avoid.digest)
 
 
 class RoadRouter:
@@ -146,6 +156,7 @@ class RoadRouter:
             self._cpu_metrics: "OrderedDict[int, Any]" = OrderedDict()
             self._cpu_costs: Dict[int, np.ndarray] = {}
             self._cpu_pins: Dict[int, int] = {}
+            self._cpu_avoid: Dict[int, Optional[AvoidSet]] = {}
             self.capacity = 32 if capacity is None else int(capacity)
         self.last_metric: Dict[str, Any] = {}
 
@@ -158,17 +169,24 @@ class RoadRouter:
         also hold it outside the LRU until :meth:`unpin` (see :meth:`pinned`)."""
         if self.gpu is not None:
             self.last_metric = dict(self.gpu.metric_for(ctx.weather, ctx.congestion, ctx.weekhour,
-                                                        ctx.driver_age, pin))
+                                                        ctx.driver_age, pin, *_avoid_args(ctx)))
             return ctx.key
         with self._lock:
             if ctx.key in self._cpu_metrics:
+                if self._cpu_avoid.get(ctx.key) != ctx.avoid:
+                    raise ValueError("avoid set: its digest is cached for a different set (a 2^-31 collision); "
+                                     "change a vertex by a microdegree or retry once that metric is evicted")
                 self._cpu_metrics.move_to_end(ctx.key)
                 self.last_metric = {"key": ctx.key, "fresh": False}
             else:
                 cost = context_costs_cpu(self.g, self.eta_model, ctx)
-                m = self.cpu.customize(cost, self._length)
+                if ctx.avoid is not None:
+                    cost = np.ascontiguousarray(cost, dtype=np.float32).copy()
+                    cost[avoid_mask(self.g, ctx.avoid).astype(bool)] = np.inf
+                m = self.cpu.customize(cost, self._length, allow_inf=ctx.avoid is not None)
                 self._cpu_metrics[ctx.key] = m
                 self._cpu_costs[ctx.key] = cost
+                self._cpu_avoid[ctx.key] = ctx.avoid
                 self.last_metric = {"key": ctx.key, "fresh": True, "customize_ms": m.customize_ms}
             if pin:
                 self._cpu_pins[ctx.key] = self._cpu_pins.get(ctx.key, 0) + 1
@@ -176,20 +194,32 @@ class RoadRouter:
             return ctx.key
 
     def _evict_cpu(self) -> None:
-        """LRU beyond ``capacity``, never a pinned metric (caller holds the lock)."""
+        """LRU beyond ``capacity``, never a pinned metric (caller holds the lock).  Metrics with
+        avoid areas share ``max(1, capacity // 4)`` of the slots, least recent of them first: new
+        polygons with every request cannot flush the contexts everyone shares."""
+        def drop(k):
+            del self._cpu_metrics[k]
+            self._cpu_costs.pop(k, None)
+            self._cpu_avoid.pop(k, None)
+        cap = max(1, self.capacity // 4)
+        while sum(1 for k in self._cpu_metrics if self._cpu_avoid.get(k) is not None) > cap:
+            k = next((k for k in self._cpu_metrics
+                      if self._cpu_avoid.get(k) is not None and k not in self._cpu_pins), None)
+            if k is None:
+                break
+            drop(k)
         while len(self._cpu_metrics) > self.capacity:
             k = next((k for k in self._cpu_metrics if k not in self._cpu_pins), None)
             if k is None:
                 return
-            del self._cpu_metrics[k]
-            self._cpu_costs.pop(k, None)
+            drop(k)
 
     def prefetch(self, ctx: RouteContext, urgent: bool = False) -> bool:
         """Queue the context's customization on the GPU router's background builder (returns at
         once; False on the CPU router, which has none)."""
         if self.gpu is None:
             return False
-        self.gpu.request_build(ctx.weather, ctx.congestion, ctx.weekhour, ctx.driver_age, urgent)
+        self.gpu.request_build(ctx.weather, ctx.congestion, ctx.weekhour, ctx.driver_age, urgent, *_avoid_args(ctx))
         return True
 
     def is_cached(self, ctx_or_key) -> bool:
@@ -232,8 +262,9 @@ class RoadRouter:
             self.last_metric = dict(self.gpu.metric_from_costs(int(key), torch.from_numpy(cost).to(self.dev)))
             return int(key)
         with self._lock:
-            self._cpu_metrics[int(key)] = self.cpu.customize(cost, self._length)
+            self._cpu_metrics[int(key)] = self.cpu.customize(cost, self._length, allow_inf=True)
             self._cpu_costs[int(key)] = cost
+            self._cpu_avoid.pop(int(key), None)
             return int(key)
 
     def costs(self, ctx_or_key) -> np.ndarray:

@@ -153,7 +153,9 @@ def parse_request(data: Any) -> Dict[str, Any]:
 def isochrones(provider, data: Any, ctx=None, device=None) -> Dict[str, Any]:
     """The endpoint's answer for a road-graph provider (``routing.graph.GraphProvider``)."""
     from .graph import median_edge_m
+    from .avoid import check_provider
     req = parse_request(data)
+    check_provider(provider, ctx)
     g = provider.g
     cell_m = req["cell_m"]
     if cell_m is None:
@@ -173,6 +175,8 @@ def isochrones(provider, data: Any, ctx=None, device=None) -> Dict[str, Any]:
                       "properties": {"group_index": r["point"], "value": r["value"],
                                      "center": [round(float(g.lon[n]), 6), round(float(g.lat[n]), 6)],
                                      "reached_nodes": r["reached_nodes"], "reach_m": round(r["reach_m"], 1)}})
-    return {"type": "FeatureCollection", "features": feats,
-            "metadata": {"range_type": req["range_type"],
-                         "location_type": "destination" if req["reverse"] else "start", "cell_m": cell_m}}
+    meta = {"range_type": req["range_type"], "location_type": "destination" if req["reverse"] else "start",
+            "cell_m": cell_m}
+    if getattr(ctx, "avoid", None) is not None:
+        meta["avoid"] = ctx.avoid.summary()
+    return {"type": "FeatureCollection", "features": feats, "metadata": meta}

@@ -629,8 +629,10 @@ def parse_match_request(data: Any) -> Tuple[List[np.ndarray], MatchParams]:
 def match_response(provider, data: Any, ctx=None, device=None) -> Dict[str, Any]:
     """The endpoint's answer for a road-graph provider: OSRM-shaped ``matchings`` / ``tracepoints``
     per trace."""
+    from .avoid import check_provider
     traces, params = parse_match_request(data)
     g = provider.g
+    check_provider(provider, ctx)
     res = provider.match(traces, ctx=ctx, params=params, device=device)
 
     def lonlat(n: int) -> List[float]:
@@ -647,4 +649,7 @@ def match_response(provider, data: Any, ctx=None, device=None) -> Dict[str, Any]
                    "matchings_index": int(r["matching"][i]), "distance": int(dist[i]) / 100.0}
                   for i in range(len(r["matched"]))]
         out.append({"matchings": matchings, "tracepoints": points})
-    return {"code": "Ok", "traces": out}
+    ans: Dict[str, Any] = {"code": "Ok", "traces": out}
+    if getattr(ctx, "avoid", None) is not None:
+        ans["avoid"] = ctx.avoid.summary()
+    return ans

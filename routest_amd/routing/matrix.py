@@ -69,10 +69,12 @@ def _cells(a: np.ndarray) -> List[List[Any]]:
 
 def matrix_response(provider, data: Any, ctx=None, device=None) -> Dict[str, Any]:
     """The endpoint's answer for a road-graph provider (``routing.graph.GraphProvider``)."""
+    from .avoid import check_provider
     from .cch import RouteContext
     req = parse_request(data)
     g = provider.g
     ctx = ctx or RouteContext()
+    check_provider(provider, ctx)
     sec, met, nodes, snap = provider.matrix_rect([{"lon": p[0], "lat": p[1]} for p in req["locations"]],
                                                  req["sources"], req["destinations"], ctx=ctx, device=device)
 
@@ -90,4 +92,6 @@ def matrix_response(provider, data: Any, ctx=None, device=None) -> Dict[str, Any
     out["destinations"] = [point(i) for i in req["destinations"]]
     out["metadata"] = {"engine": "cch", "context": {"weather": int(ctx.weather), "congestion": int(ctx.congestion),
                                                     "weekhour": int(ctx.weekhour)}}
+    if ctx.avoid is not None:
+        out["metadata"]["context"]["avoid"] = ctx.avoid.summary()
     return out

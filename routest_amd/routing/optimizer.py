@@ -157,12 +157,35 @@ def optimize_route(input_data: Any, provider, engine: str = "backend:mi355x",
     if not isinstance(source, dict) or "lat" not in source or "lon" not in source:
         return {"error": "source_point with lat/lon is required."}
     destinations = input_data["destination_points"]
-    # road providers route under the request's context (weather, traffic, pickup week-hour)
+    # road providers route under the request's context (weather, traffic, pickup week-hour, and
+    # the areas options.avoid_polygons closes)
+    from .avoid import NEEDS_CCH, parse_options
+    try:
+        avoid = parse_options(input_data)
+    except ValueError as e:
+        return {"error": str(e)}
     if not getattr(provider, "uses_context", False):
+        if avoid is not None:
+            return {"error": NEEDS_CCH}
         ctx = None
     elif ctx is None:
         from .cch import RouteContext
         ctx = RouteContext.from_request(input_data)
+    if avoid is None:
+        return _optimize(input_data, provider, engine, trips, ctx, improvement, driver, vehicle_type, profile,
+                         source, destinations)
+    try:
+        feature = _optimize(input_data, provider, engine, trips, ctx, improvement, driver, vehicle_type, profile,
+                            source, destinations)
+    except ValueError as e:                     # the set's digest is cached for another set (routing/cch.py)
+        return {"error": str(e)}
+    if "error" not in feature:
+        feature.setdefault("properties", {})["avoid"] = avoid.summary()
+    return feature
+
+
+def _optimize(input_data, provider, engine, trips, ctx, improvement, driver, vehicle_type, profile, source,
+              destinations) -> Dict[str, Any]:
     if len(destinations) == 1:
         feature = point_to_point(provider, source, destinations[0], profile, driver, ctx)
         if "error" in feature:

@@ -143,7 +143,15 @@ class RouteBatcher:
         import datetime as dt
         from .cch import RouteContext
         now = dt.datetime.now()
-        return [RouteContext.from_request(p, now=now) if _valid_points(p) else None for p in payloads]
+
+        def one(p):
+            if not _valid_points(p):
+                return None
+            try:
+                return RouteContext.from_request(p, now=now)
+            except ValueError as e:         # a malformed options.avoid_polygons fails its own request
+                return ProviderError(str(e))
+        return [one(p) for p in payloads]
 
     def _graph_plan(self, payloads: List[Any], device, ctxs: List[Any]) -> tuple:
         """Road-graph flush: per routing context, ONE many-to-many launch for every multi-stop
@@ -159,20 +167,26 @@ class RouteBatcher:
         stats: Dict[int, Any] = {}
         legs: Dict[tuple, tuple] = {}
         host_costs: Dict[int, np.ndarray] = {}
-        valid = [k for k, r in enumerate(payloads) if _valid_points(r)]
+        valid = [k for k, r in enumerate(payloads) if _valid_points(r) and not isinstance(ctxs[k], ProviderError)]
         if not valid:
             return trips, legs, host_costs, stats
         groups: Dict[Any, List[int]] = {}
         first: Dict[Any, Any] = {}
         for k in valid:
-            gk = ctxs[k].key if ctxs[k] is not None else None
+            # (two avoid sets of one digest share a key: separate groups, the second one fails below)
+            gk = (ctxs[k].key, ctxs[k].avoid) if ctxs[k] is not None else None
             groups.setdefault(gk, []).append(k)
             first.setdefault(gk, ctxs[k])
         for gk, ks in groups.items():
-            with prov.pinned_metric(first[gk], device) as key:
-                self._plan_group(payloads, ks, key, device, trips, legs, stats)
-                if getattr(prov, "_steps", None) is not None:
-                    host_costs[key] = prov.edge_seconds(key, device)
+            try:
+                with prov.pinned_metric(first[gk], device) as key:
+                    self._plan_group(payloads, ks, key, device, trips, legs, stats)
+                    if getattr(prov, "_steps", None) is not None:
+                        host_costs[key] = prov.edge_seconds(key, device)
+            except ValueError as e:
+                if first[gk] is None or first[gk].avoid is None:
+                    raise
+                trips.update({k: ProviderError(str(e)) for k in ks})
         return trips, legs, host_costs, stats
 
     def _plan_group(self, payloads, ks, key, device, trips, legs, stats) -> None:
@@ -263,7 +277,8 @@ class RouteBatcher:
             except ProviderError as e:
                 return [(e, None, None, None) for _ in payloads]
             view = _LegView(self.provider, legs, device, hc)
-            return [(trips.get(k), view, ctxs[k], stats.get(k)) for k in range(len(payloads))]
+            return [(ctxs[k], None, None, None) if isinstance(ctxs[k], ProviderError) else
+                    (trips.get(k), view, ctxs[k], stats.get(k)) for k in range(len(payloads))]
         multi = [k for k, r in enumerate(payloads) if _valid_points(r) and len(r["destination_points"]) > 1]
         if multi and name in ("haversine", "graph"):
             res, st = batched_trips([payloads[k] for k in multi], circuity=self.provider.circuity,
