@@ -548,6 +548,50 @@ std::vector<torch::Tensor> route_exchange_trips(torch::Tensor D, torch::Tensor n
   return {moves, rejected, tbefore, tafter, before, after};
 }
 
+// K6d: rows with flag != 0 are planned under their time windows (routing/timewindows.py).  Returns
+// (visit, trip_of i32 [R,NM] in K6's layout, ntrips, status i32 [R], arrival_q, start_q i64 [R,NM]
+// per visit position, stats i64 [R,4] = insertions, rejected, len_q, waiting_q).  Rows with
+// flag == 0 keep the fill: -1 in the four [R,NM] outputs, 0 elsewhere.
+std::vector<torch::Tensor> route_tw_trips(torch::Tensor D, torch::Tensor T, torch::Tensor npts,
+                                          torch::Tensor demand, torch::Tensor cap, torch::Tensor maxd,
+                                          torch::Tensor open, torch::Tensor close, torch::Tensor service,
+                                          torch::Tensor flag) {
+  for (auto* t : {&D, &T, &npts, &demand, &cap, &maxd, &open, &close, &service, &flag})
+    check_dev(*t, "route tensor");
+  TORCH_CHECK(D.scalar_type() == torch::kFloat64 && D.dim() == 3 && D.size(1) == D.size(2),
+              "D must be f64 [R,NM,NM]");
+  TORCH_CHECK(T.scalar_type() == torch::kFloat64 && T.sizes() == D.sizes(), "T must be f64 [R,NM,NM]");
+  const int R = (int)D.size(0), NM = (int)D.size(1);
+  TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
+  TORCH_CHECK(npts.scalar_type() == torch::kInt32 && npts.numel() == R, "npts must be i32 [R]");
+  TORCH_CHECK(demand.scalar_type() == torch::kFloat64 && demand.numel() == (int64_t)R * NM,
+              "demand must be f64 [R,NM]");
+  TORCH_CHECK(cap.scalar_type() == torch::kFloat64 && cap.numel() == R, "cap must be f64 [R]");
+  TORCH_CHECK(maxd.scalar_type() == torch::kFloat64 && maxd.numel() == R, "maxd must be f64 [R]");
+  for (auto* t : {&open, &close, &service})
+    TORCH_CHECK(t->scalar_type() == torch::kInt64 && t->numel() == (int64_t)R * NM,
+                "open, close and service must be i64 [R,NM] (milliseconds)");
+  TORCH_CHECK(flag.scalar_type() == torch::kUInt8 && flag.numel() == R, "flag must be u8 [R]");
+  const c10::DeviceGuard guard(D.device());
+  auto iopt = D.options().dtype(torch::kInt32);
+  auto lopt = D.options().dtype(torch::kInt64);
+  auto visit = torch::full({R, NM}, -1, iopt);
+  auto trip_of = torch::full({R, NM}, -1, iopt);
+  auto ntrips = torch::zeros({R}, iopt);
+  auto status = torch::zeros({R}, iopt);
+  auto arrival = torch::full({R, NM}, -1, lopt);
+  auto start = torch::full({R, NM}, -1, lopt);
+  auto stats = torch::zeros({R, 4}, lopt);
+  RT_CHECK_HIP(rt::launch_tw_trips(
+      D.data_ptr<double>(), T.data_ptr<double>(), npts.data_ptr<int>(), demand.data_ptr<double>(),
+      cap.data_ptr<double>(), maxd.data_ptr<double>(), (const long long*)open.data_ptr<int64_t>(),
+      (const long long*)close.data_ptr<int64_t>(), (const long long*)service.data_ptr<int64_t>(),
+      flag.data_ptr<uint8_t>(), R, NM, visit.data_ptr<int>(), trip_of.data_ptr<int>(), ntrips.data_ptr<int>(),
+      status.data_ptr<int>(), (long long*)arrival.data_ptr<int64_t>(), (long long*)start.data_ptr<int64_t>(),
+      (long long*)stats.data_ptr<int64_t>(), cur_stream(D)));
+  return {visit, trip_of, ntrips, status, arrival, start, stats};
+}
+
 // K10 candidates: (cand i32 [P,k], cand_d2 i64 [P,k], n_cand i32 [P]) of the fixes (py, px) on the
 // graph's bucket grid (routing/mapmatch.py build_grid).
 std::vector<torch::Tensor> mm_candidates(torch::Tensor start, torch::Tensor items, torch::Tensor nqy,
@@ -1555,6 +1599,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("route_greedy_cvrp", &route_greedy_cvrp, "K6: batched greedy multi-trip CVRP");
   m.def("route_improve_trips", &route_improve_trips,
         "K6b: intra-trip 2-opt / Or-opt on K6's outputs (visit rewritten in place)");
+  m.def("route_tw_trips", &route_tw_trips,
+        "K6d: cheapest-insertion trips under time windows and service times for the flagged rows",
+        py::arg("D"), py::arg("T"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"),
+        py::arg("open"), py::arg("close"), py::arg("service"), py::arg("flag"));
   m.def("route_exchange_trips", &route_exchange_trips,
         "K6c: inter-trip relocate / swap on K6's outputs (visit, trip_of, ntrips rewritten in place)",
         py::arg("D"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"), py::arg("visit"),

@@ -230,6 +230,18 @@ hipError_t launch_improve_trips(const double* D, const int* npts, const double* 
                                 long long* len_before_q, long long* len_after_q,
                                 hipStream_t stream);
 
+// ---- K6d cheapest-insertion trips under time windows : route_tw.hip ----
+// Rows with flag != 0 are planned (routing/timewindows.py): visit / trip_of in K6's layout, ntrips,
+// status (0 ok, 1 a stop cannot be served alone: visit lists the stops that can, 2 more than 128
+// stops), arrival / start milliseconds per visit position, stats [R, 4] = insertions, rejected,
+// len_q, waiting_q.  Rows with flag == 0 are not touched.  open / close / service: [R, NM] int64
+// milliseconds per point (column 0 ignored), 0 <= open, service <= 2^31, 0 <= close <= 2^62.
+hipError_t launch_tw_trips(const double* D, const double* T, const int* npts, const double* demand,
+                           const double* cap, const double* maxd, const long long* open,
+                           const long long* close, const long long* service, const unsigned char* flag,
+                           int R, int NM, int* visit, int* trip_of, int* ntrips, int* status,
+                           long long* arrival, long long* start, long long* stats, hipStream_t stream);
+
 // ---- K6c inter-trip relocate / swap on K6's outputs : route_exchange.hip ----
 // visit, trip_of and ntrips are rewritten in place for rows with flag != 0 and status == 0 (still
 // grouped by trip, trip indices compacted); the six statistics are written for every row (0 for

@@ -647,7 +647,8 @@ bool RouteService::submit(RouteJob* j) {
     p_->n_jobs.fetch_add(1, std::memory_order_relaxed);
     Impl::parse_job(j);
   }
-  if (j->req.avoid) return false;   // avoid areas: the app answers, no flush waits for this job
+  // avoid areas, time windows: the app answers, no flush waits for this job
+  if (j->req.avoid || j->req.time_windows) return false;
   {
     std::lock_guard<std::mutex> lk(p_->mu);
     if (p_->stop) return false;   // the run loop may have drained its queue already

@@ -366,6 +366,93 @@ static void fuzz_exchange(std::mt19937_64& rng, int iters) {
   }
 }
 
+// route_core.h tw_trips: on random metres / seconds matrices (asymmetric, with NaN / inf / negative /
+// huge entries) and random windows and service times, either some stop is reported infeasible alone
+// (indices in range, ascending) or every stop is placed exactly once, every trip re-simulates as
+// feasible on usable entries only, the reported arrivals / starts are the re-simulated ones, and the
+// statistics are the measured ones
+static void fuzz_tw(std::mt19937_64& rng, int iters) {
+  for (int it = 0; it < iters / 100; ++it) {
+    const int n1 = 1 + (int)(rng() % 34);
+    std::vector<double> d((size_t)n1 * n1, 0.0), t((size_t)n1 * n1, 0.0), dem(n1, 0.0);
+    for (int a = 0; a < n1; ++a)
+      for (int b = 0; b < n1; ++b)
+        if (a != b) {
+          d[(size_t)a * n1 + b] = 100.0 + (double)(rng() % 1000000) / 37.0;
+          t[(size_t)a * n1 + b] = 10.0 + (double)(rng() % 100000) / 53.0;
+        }
+    if (rng() % 3 == 0 && n1 > 4) {
+      const double bad[6] = {NAN, INFINITY, -5.0, 2147483.647, 3e9, 1e300};
+      for (int x = 0; x < 6; ++x) {
+        std::vector<double>& m = rng() % 2 ? d : t;
+        // mostly between stops; now and then on a depot leg, which makes a stop infeasible alone
+        const int a = rng() % 8 == 0 ? 0 : 1 + (int)(rng() % (n1 - 1)), b = 1 + (int)(rng() % (n1 - 1));
+        if (a != b) m[(size_t)a * n1 + b] = bad[rng() % 6];
+      }
+    }
+    std::vector<long long> open(n1, 0), close(n1, rtr::kExchangeUnbounded), sv(n1, 0);
+    for (int s = 1; s < n1; ++s) {
+      dem[s] = (double)(1 + rng() % 3);
+      if (rng() % 10 < 7) {
+        open[s] = (long long)(rng() % 20000000);
+        close[s] = open[s] + (long long)(rng() % 3 == 0 ? 0 : rng() % 8000000);
+        if (rng() % 4 == 0) open[s] = 0;
+      }
+      if (rng() % 2) sv[s] = (long long)(rng() % 600000);
+    }
+    if (rng() % 16 == 0 && n1 > 1) dem[1 + rng() % (n1 - 1)] = rng() % 2 ? NAN : -1.0;
+    const bool free_run = rng() % 3 == 0;
+    const double cap = free_run ? 9e12 : (rng() % 16 == 0 ? NAN : (double)(3 + rng() % 30));
+    const double maxd = free_run ? 9e12 : (rng() % 16 == 0 ? -1.0 : 60000.0 + (double)(rng() % 400000));
+    std::vector<std::vector<int>> trips;
+    std::vector<std::vector<long long>> arr, sta;
+    std::vector<int> bad;
+    rtr::TwStats st;
+    if (!rtr::tw_trips(d, t, n1, dem, cap, maxd, open, close, sv, trips, arr, sta, bad, st)) {
+      CHECK(!bad.empty() && trips.empty(), "tw_trips failed without naming a stop");
+      for (size_t x = 0; x < bad.size(); ++x)
+        CHECK(bad[x] >= 0 && bad[x] < n1 - 1 && (x == 0 || bad[x] > bad[x - 1]), "tw_trips infeasible index %d", bad[x]);
+      continue;
+    }
+    std::vector<int> seen(n1, 0);
+    long long len = 0, waiting = 0;
+    CHECK(trips.size() == arr.size() && trips.size() == sta.size() && st.trips == (long long)trips.size(), "tw_trips trip counts");
+    for (size_t k = 0; k < trips.size(); ++k) {
+      const std::vector<int>& tr = trips[k];
+      CHECK(tr.size() >= 3 && tr.front() == 0 && tr.back() == 0, "tw_trips broke a trip's ends");
+      CHECK(arr[k].size() + 2 == tr.size() && sta[k].size() + 2 == tr.size(), "tw_trips schedule length");
+      long long clock = 0;
+      bool ok = true;
+      for (size_t p = 0; p + 1 < tr.size(); ++p) {
+        const int a = tr[p], b = tr[p + 1];
+        if (a < 0 || a >= n1 || b < 0 || b >= n1) { ok = false; break; }
+        const long long q = rtr::tw_q(d[(size_t)a * n1 + b]), qt = rtr::tw_q(t[(size_t)a * n1 + b]);
+        ok = ok && q < rtr::kImproveBig && qt < rtr::kImproveBig;
+        len += q;
+        if (b == 0) break;
+        ++seen[b];
+        const long long ar = clock + qt, s0 = std::max(ar, open[b]);
+        ok = ok && s0 <= close[b] && p < arr[k].size() && arr[k][p] == ar && sta[k][p] == s0;
+        waiting += s0 - ar;
+        clock = s0 + sv[b];
+      }
+      CHECK(ok, "tw_trips built a trip that does not re-simulate as feasible");
+      double s = 0.0, load = 0.0;
+      const int kk = (int)tr.size() - 2;
+      for (int p = 0; p < kk; ++p) s += d[(size_t)tr[p] * n1 + tr[p + 1]];
+      for (int p = 1; p <= kk; ++p) load += dem[tr[p]];
+      CHECK(s + d[(size_t)tr[kk] * n1] <= maxd && load <= cap, "tw_trips kept a trip that fails the float walks");
+    }
+    bool once = true;
+    for (int s = 1; s < n1; ++s) once = once && seen[s] == 1;
+    CHECK(once, "tw_trips lost or repeated a stop");
+    CHECK(len == st.len_q && waiting == st.waiting_q, "tw_trips statistics: len %lld / %lld, waiting %lld / %lld", st.len_q, len,
+          st.waiting_q, waiting);
+    CHECK(st.insertions + st.trips == (long long)(n1 - 1), "tw_trips: %lld insertions + %lld trips != %d stops", st.insertions,
+          st.trips, n1 - 1);
+  }
+}
+
 // map_match.h mm_candidates: on random node sets (clusters, duplicates, one line) and fixes inside,
 // on and far outside the grid the answer equals a scan of all nodes sorted by (d2, node id)
 static void fuzz_mm_candidates(std::mt19937_64& rng, int iters) {
@@ -868,6 +955,7 @@ int main(int argc, char** argv) {
   fuzz_coord_cache(rng, iters);
   fuzz_improve(rng, iters);
   fuzz_exchange(rng, iters);
+  fuzz_tw(rng, iters);
   fuzz_alternatives(rng, iters);
   fuzz_history(rng, iters);
   fuzz_mm_candidates(rng, iters);

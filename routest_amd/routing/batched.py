@@ -9,6 +9,8 @@ are re-sequenced by the intra-trip 2-opt / Or-opt of :mod:`routing.improve` (on 
 launch, K6b, on K6's own tensors) and the call returns ``(results, stats)``, ``stats[k]`` being the
 request's improvement statistics or ``None``.  Per-request ``exchange`` flags add the inter-trip
 relocate / swap search of :mod:`routing.exchange` between two such passes (on a GPU K6b, K6c, K6b).
+Requests given ``time_windows`` are planned by the cheapest insertion of :mod:`routing.timewindows`
+instead (on a GPU one launch, K6d, over the flagged rows only).
 Sharding over several GPUs is done by
 :class:`routing.route_batcher.RouteBatcher` (one worker thread per device, no collective).
 """
@@ -21,9 +23,10 @@ import torch
 
 from ..ops import _ext
 from .greedy import InfeasibleStops, greedy_trips
-from .exchange import improve_exchange_trips
+from .exchange import UNBOUNDED, improve_exchange_trips
 from .improve import improve_trips
 from .providers import haversine_matrix
+from .timewindows import MAX_STOPS as TW_MAX_STOPS, tw_trips
 
 TripsOrError = Union[List[List[int]], InfeasibleStops]
 
@@ -96,9 +99,68 @@ def _both_flags(improve, exchange, R: int):
     return (zeros if flags is None else flags), (zeros if xflags is None else xflags)
 
 
+def pack_time_windows(requests: Sequence[Dict[str, Any]], time_windows: Sequence[Any], nm: int):
+    """``time_windows[k]``: None, or the ``(open_q, close_q, sv_q)`` of
+    :func:`timewindows.parse_time_windows` for request ``k``.  Returns ``(open, close, service``
+    int64 [R, nm] milliseconds, ``flags`` uint8 [R], ``speed`` float64 [R]: the request profile's
+    metres per second, which turns a haversine matrix into seconds)."""
+    from .providers import PROFILE_SPEED_MPS, profile_for
+    R = len(requests)
+    if len(time_windows) != R:
+        raise ValueError(f"time_windows must hold one entry per request ({R}), got {len(time_windows)}")
+    op = np.zeros((R, nm), dtype=np.int64)
+    cl = np.full((R, nm), UNBOUNDED, dtype=np.int64)
+    sv = np.zeros((R, nm), dtype=np.int64)
+    flags = np.zeros(R, dtype=np.uint8)
+    speed = np.ones(R)
+    for k, (r, tw) in enumerate(zip(requests, time_windows)):
+        if tw is None:
+            continue
+        n = 1 + len(r["destination_points"])
+        if n - 1 > TW_MAX_STOPS or any(len(v) != n for v in tw):
+            raise ValueError(f"time_windows[{k}] must hold one entry per point, at most {TW_MAX_STOPS} stops")
+        flags[k] = 1
+        op[k, :n], cl[k, :n], sv[k, :n] = tw
+        drv = r.get("driver_details") or {}
+        profile = profile_for(drv.get("vehicle_type") if isinstance(drv, dict) else None)
+        speed[k] = PROFILE_SPEED_MPS.get(profile, PROFILE_SPEED_MPS["driving-car"])
+    return op, cl, sv, flags, speed
+
+
+def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw):
+    """K6d over the flagged rows: ``{row: trips or InfeasibleStops}``, ``{row: (schedule, stats)}``."""
+    op, cl, sv, twf, speed = tw
+    if T is None:
+        # one IEEE division per entry, as HaversineProvider.time_matrix does it on the host
+        T = D / t(speed).reshape(-1, 1, 1)
+    else:
+        T = t(np.ascontiguousarray(T, dtype=np.float64))
+    out = C.route_tw_trips(D, T.contiguous(), npts_t, dem_t, cap_t, maxd_t, t(op, torch.int64),
+                           t(cl, torch.int64), t(sv, torch.int64), t(twf, torch.uint8))
+    visit, trip_of, ntrips, status, arr, start, stats = (c.cpu().numpy() for c in out)
+    rows = np.flatnonzero(twf)
+    if (status[rows] > 1).any():
+        raise ValueError(f"time-window rows take at most {TW_MAX_STOPS} stops")
+    trips = _unpack(visit[rows], trip_of[rows], ntrips[rows], status[rows], np.asarray(npts)[rows], None)
+    res, sched = {}, {}
+    for x, k in enumerate(rows.tolist()):
+        if isinstance(trips[x], InfeasibleStops):
+            res[k] = InfeasibleStops(trips[x].stops, time_windows=True)
+            continue
+        res[k] = trips[x]
+        one, p = [], 0
+        for trip in trips[x]:
+            one.append([(s, int(arr[k, p + i]), int(start[k, p + i]), int(start[k, p + i]) + int(sv[k, s]))
+                        for i, s in enumerate(trip[1:-1])])
+            p += len(trip) - 2
+        sched[k] = (one, {"insertions": int(stats[k, 0]), "rejected": int(stats[k, 1]), "trips": len(trips[x]),
+                          "len_q": int(stats[k, 2]), "waiting_q": int(stats[k, 3])})
+    return res, sched
+
+
 def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device,
                          D: Optional[np.ndarray] = None, improve: Optional[Sequence[Any]] = None,
-                         exchange: Optional[Sequence[Any]] = None):
+                         exchange: Optional[Sequence[Any]] = None, tw=None, T: Optional[np.ndarray] = None):
     # K6 indexes its LDS order / visited arrays by stop number: a request longer than the padded
     # width would write past them, so it is refused here, before anything reaches the device
     nm = int(D.shape[1]) if D is not None else int(np.shape(lat)[1])
@@ -114,6 +176,9 @@ def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device
     else:
         D = t(np.ascontiguousarray(D, dtype=np.float64))
     flags, xflags = _both_flags(improve, exchange, len(n))
+    if tw is not None and flags is not None:
+        # improve / exchange know nothing of windows: a time-window row ignores them
+        flags, xflags = flags & ~tw[3] & 1, xflags & ~tw[3] & 1
     npts_t, maxd_t, dem_t, cap_t = t(npts, torch.int32), t(maxd), t(dem), t(cap)
     visit, trip_of, ntrips, status = C.route_greedy_cvrp(D, npts_t, dem_t, cap_t, maxd_t)
     stats = xstats = stats3 = None
@@ -132,7 +197,18 @@ def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device
     status_h = status.cpu().numpy()
     out = _unpack(visit.cpu().numpy(), trip_of.cpu().numpy(), ntrips.cpu().numpy(), status_h,
                   npts, D.cpu().numpy())
-    if flags is None:
+    if tw is not None:
+        # K6d plans the flagged rows (a batch nobody flags launches nothing); the others keep K6's
+        twres: List[Any] = [None] * len(n)
+        if tw[3].any():
+            planned, sched = _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw)
+            for k, v in planned.items():
+                out[k] = v
+                twres[k] = sched.get(k)
+            status_h = np.where(tw[3] != 0, 1, status_h)      # no improvement statistics for these rows
+        if flags is None:
+            return out, [None] * len(n), twres
+    elif flags is None:
         return out
     cols = [c.cpu().numpy() for c in stats] if stats is not None else None
     xcols = [c.cpu().numpy() for c in xstats] if xstats is not None else None
@@ -147,19 +223,34 @@ def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device
         else:
             res[k] = {"moves": int(cols[0][k]), "trips_changed": int(cols[1][k]),
                       "len_before_q": int(cols[2][k]), "len_after_q": int(cols[3][k])}
-    return out, res
+    return (out, res) if tw is None else (out, res, twres)
 
 
 def batched_trips_cpu(lat, lon, dem, npts, cap, maxd, circuity: float,
                       D: Optional[np.ndarray] = None, improve: Optional[Sequence[Any]] = None,
-                      exchange: Optional[Sequence[Any]] = None):
+                      exchange: Optional[Sequence[Any]] = None, tw=None, T: Optional[np.ndarray] = None):
     out: List[TripsOrError] = []
     flags, xflags = _both_flags(improve, exchange, len(npts))
     stats: List[Optional[Dict[str, int]]] = []
+    twres: List[Any] = []
     for k in range(len(npts)):
         n = int(npts[k])
         d = D[k, :n, :n] if D is not None else haversine_matrix(lat[k, :n], lon[k, :n], circuity)
         st = None
+        if tw is not None and tw[3][k]:
+            # the reference of K6d (routing/timewindows.py); improve / exchange are ignored
+            sec = T[k, :n, :n] if T is not None else np.asarray(d, dtype=np.float64) / tw[4][k]
+            try:
+                trips, sched, tst = tw_trips(d, sec, dem[k, :n].tolist(), float(cap[k]), float(maxd[k]),
+                                             tw[0][k, :n], tw[1][k, :n], tw[2][k, :n])
+                out.append(trips)
+                twres.append((sched, tst))
+            except InfeasibleStops as e:
+                out.append(e)
+                twres.append(None)
+            stats.append(None)
+            continue
+        twres.append(None)
         try:
             trips = greedy_trips(d.tolist(), dem[k, :n].tolist(), float(cap[k]), float(maxd[k]))
             if flags is not None and xflags[k]:
@@ -171,20 +262,38 @@ def batched_trips_cpu(lat, lon, dem, npts, cap, maxd, circuity: float,
         except InfeasibleStops as e:
             out.append(e)
         stats.append(st)
+    if tw is not None:
+        return out, stats, twres
     return out if flags is None else (out, stats)
 
 
 def batched_trips(requests: Sequence[Dict[str, Any]], circuity: float = 1.3,
                   device: Optional[Any] = None, D: Optional[np.ndarray] = None,
                   improve: Optional[Sequence[Any]] = None,
-                  exchange: Optional[Sequence[Any]] = None):
+                  exchange: Optional[Sequence[Any]] = None,
+                  time_windows: Optional[Sequence[Any]] = None, T: Optional[np.ndarray] = None):
     """``D``: given distance matrices [R, nm, nm] (road metres from the CCH router) instead of the
     haversine K5.  ``improve`` / ``exchange``: one flag per request; when either is given, returns
-    ``(results, stats)``.  ``exchange`` implies ``improve`` (:mod:`routing.exchange`)."""
+    ``(results, stats)``.  ``exchange`` implies ``improve`` (:mod:`routing.exchange`).
+
+    ``time_windows``: per request None or the ``(open_q, close_q, sv_q)`` of
+    :func:`timewindows.parse_time_windows`; those requests are planned by the cheapest insertion of
+    :mod:`routing.timewindows` (on a GPU one launch, K6d) and ignore ``improve`` / ``exchange``, the
+    others are planned as without the argument.  ``T``: the seconds matrices that go with ``D``
+    (without ``D``: haversine metres over the request profile's speed).  When given, the call
+    returns ``(results, stats, tw)`` with ``tw[k]`` None or ``(schedule, statistics)``."""
+    if time_windows is not None and (D is None) != (T is None):
+        raise ValueError("time windows on given matrices need both D (metres) and T (seconds)")
     if not requests:
+        if time_windows is not None:
+            return [], [], []
         return [] if improve is None and exchange is None else ([], [])
     packed = pack_requests(requests)
+    tw = None
+    if time_windows is not None:
+        nm = int(D.shape[1]) if D is not None else int(packed[0].shape[1])
+        tw = pack_time_windows(requests, time_windows, nm)
     if device is not None and torch.device(device).type == "cuda":
         return batched_trips_device(*packed, circuity=circuity, device=device, D=D, improve=improve,
-                                    exchange=exchange)
-    return batched_trips_cpu(*packed, circuity=circuity, D=D, improve=improve, exchange=exchange)
+                                    exchange=exchange, tw=tw, T=T)
+    return batched_trips_cpu(*packed, circuity=circuity, D=D, improve=improve, exchange=exchange, tw=tw, T=T)

@@ -681,6 +681,17 @@ class GraphProvider(HaversineProvider):
             _, met = self.router().matrix(list(map(int, nodes)), key)
         return met.astype(np.float64)
 
+    def time_matrix(self, points: List[Dict[str, float]], profile: str, ctx=None):
+        """``(seconds, metres)`` float64 [n, n] of the time-shortest paths under the request's context,
+        as the CCH router returns them (time-window planning, routing/timewindows.py)."""
+        if self.engine == "astar":
+            from .timewindows import NEEDS_MATRIX_TIMES
+            raise ProviderError(NEEDS_MATRIX_TIMES)
+        nodes = self.g.nearest_nodes([p["lat"] for p in points], [p["lon"] for p in points])
+        with self.pinned_metric(ctx) as key:
+            sec, met = self.router().matrix(list(map(int, nodes)), key)
+        return sec.astype(np.float64), met.astype(np.float64)
+
     def matrix_rect(self, points: List[Dict[str, float]], sources: Sequence[int], destinations: Sequence[int],
                     ctx=None, device=None):
         """Rectangular road matrix between snapped points (``POST /api/matrix``): ``sources`` /

@@ -31,10 +31,12 @@ from typing import List, Sequence
 
 
 class InfeasibleStops(ValueError):
-    def __init__(self, stops: Sequence[int]):
+    def __init__(self, stops: Sequence[int], time_windows: bool = False):
         self.stops = list(stops)
+        # a time-window request (routing/timewindows.py) has one more way to fail
+        more = " or its time window cannot be met" if time_windows else ""
         super().__init__("infeasible stop(s) (payload exceeds vehicle capacity or round trip "
-                         f"exceeds maximum_distance): destination indices {self.stops}")
+                         f"exceeds maximum_distance{more}): destination indices {self.stops}")
 
 
 def greedy_trips(d: Sequence[Sequence[float]], demand: Sequence[float], cap: float,

@@ -32,6 +32,8 @@ from .greedy import InfeasibleStops, greedy_trips, optimized_order
 from .exchange import improve_exchange_trips, wants_exchange
 from .improve import improve_trips, improvement_properties, wants_improve
 from .providers import ProviderError, _bbox, profile_for
+from .timewindows import (NEEDS_MATRIX_TIMES, parse_time_windows, schedule_properties, tw_trips,
+                          wants_time_windows)
 
 
 def _annotate(feature: Dict[str, Any], driver: Dict[str, Any], vehicle_type: str, engine: str) -> None:
@@ -113,11 +115,36 @@ def assemble_trips(provider, all_points: List[Dict[str, Any]], trips: List[List[
 
 def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, Any],
                trips: Optional[List[List[int]]] = None, ctx=None, improve: bool = False,
-               improvement: Optional[Dict[str, int]] = None, exchange: bool = False) -> Dict[str, Any]:
+               improvement: Optional[Dict[str, int]] = None, exchange: bool = False,
+               tw=None, tw_result=None) -> Dict[str, Any]:
     """``improve``: re-sequence the trips built here (routing/improve.py); ``exchange``: also move
     stops between them (routing/exchange.py; it implies ``improve``).  Trips given by the caller
-    are taken as they are; ``improvement`` holds their statistics if they were improved."""
+    are taken as they are; ``improvement`` holds their statistics if they were improved.
+    ``tw``: the request's ``(open_q, close_q, sv_q)`` (routing/timewindows.py): the trips are built
+    by cheapest insertion under the windows, ``improve`` / ``exchange`` are ignored and the response
+    carries ``schedule`` / ``time_windows``; ``tw_result``: the ``(schedule, statistics)`` of given trips."""
     all_points = [source] + list(destinations)
+    if tw is not None and tw_result is None:
+        # (trips that come without their schedule were not planned under the windows)
+        if not hasattr(provider, "time_matrix"):
+            return {"error": NEEDS_MATRIX_TIMES}
+        try:
+            sec, d = provider.time_matrix(all_points, profile, **_ctx_kw(ctx))
+        except ProviderError as e:
+            return {"error": str(e)}
+        demand = [0.0] + [_float(p.get("payload", 0), 0.0) for p in destinations]
+        try:
+            trips, schedule, tstats = tw_trips(d, sec, demand, _float(driver.get("vehicle_capacity", 9e12), 9e12),
+                                               _float(driver.get("maximum_distance", 9e12), 9e12), *tw)
+        except InfeasibleStops as e:
+            return {"error": str(e)}
+        tw_result = (schedule, tstats)
+    if tw is not None:
+        feature = assemble_trips(provider, all_points, trips, profile, source, destinations, ctx)
+        if "error" not in feature and tw_result is not None:
+            p = feature["properties"]
+            p["schedule"], p["time_windows"] = schedule_properties(tw_result[0], tw_result[1], tw[1])
+        return feature
     if trips is None:
         try:
             d = provider.matrix(all_points, profile, **_ctx_kw(ctx))
@@ -143,11 +170,12 @@ def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, A
 
 def optimize_route(input_data: Any, provider, engine: str = "backend:mi355x",
                    trips: Optional[List[List[int]]] = None, ctx=None,
-                   improvement: Optional[Dict[str, int]] = None) -> Dict[str, Any]:
+                   improvement: Optional[Dict[str, int]] = None, tw_result=None) -> Dict[str, Any]:
     """Pure function: GeoJSON Feature on success, ``{"error": ...}`` on failure (R19).  ``ctx``:
     the request's routing context as resolved when its legs were planned (the batcher), so a
     request without ``pickup_time`` is assembled under the same week-hour it was routed in.
-    ``improvement``: the statistics of given ``trips`` that were already improved (the batcher)."""
+    ``improvement``: the statistics of given ``trips`` that were already improved (the batcher);
+    ``tw_result``: the ``(schedule, statistics)`` of given ``trips`` of a time-window request."""
     if not input_data or not isinstance(input_data, dict) or not input_data.get("destination_points"):
         return {"error": "no destination points specified."}
     driver = input_data.get("driver_details") or {}
@@ -173,10 +201,10 @@ def optimize_route(input_data: Any, provider, engine: str = "backend:mi355x",
         ctx = RouteContext.from_request(input_data)
     if avoid is None:
         return _optimize(input_data, provider, engine, trips, ctx, improvement, driver, vehicle_type, profile,
-                         source, destinations)
+                         source, destinations, tw_result)
     try:
         feature = _optimize(input_data, provider, engine, trips, ctx, improvement, driver, vehicle_type, profile,
-                            source, destinations)
+                            source, destinations, tw_result)
     except ValueError as e:                     # the set's digest is cached for another set (routing/cch.py)
         return {"error": str(e)}
     if "error" not in feature:
@@ -185,7 +213,7 @@ def optimize_route(input_data: Any, provider, engine: str = "backend:mi355x",
 
 
 def _optimize(input_data, provider, engine, trips, ctx, improvement, driver, vehicle_type, profile, source,
-              destinations) -> Dict[str, Any]:
+              destinations, tw_result=None) -> Dict[str, Any]:
     if len(destinations) == 1:
         feature = point_to_point(provider, source, destinations[0], profile, driver, ctx)
         if "error" in feature:
@@ -196,9 +224,15 @@ def _optimize(input_data, provider, engine, trips, ctx, improvement, driver, veh
         p["destinations"] = [destinations[0]]
         _annotate(feature, driver, vehicle_type, engine)
         return feature
+    tw = None
+    if wants_time_windows(input_data):
+        try:
+            tw = parse_time_windows(input_data)
+        except ValueError as e:
+            return {"error": str(e)}
     feature = multi_stop(provider, source, destinations, profile, driver, trips, ctx,
                          improve=wants_improve(input_data), improvement=improvement,
-                         exchange=wants_exchange(input_data))
+                         exchange=wants_exchange(input_data), tw=tw, tw_result=tw_result)
     if "error" in feature:
         return feature
     _annotate(feature, driver, vehicle_type, engine)
@@ -216,17 +250,40 @@ def optimize_many(requests: Sequence[Dict[str, Any]], provider, engine: str = "b
              and len(r["destination_points"]) > 1 and isinstance(r.get("source_point"), dict)]
     trip_map: Dict[int, Any] = {}
     stat_map: Dict[int, Any] = {}
+    tw_map: Dict[int, Any] = {}
     if multi and getattr(provider, "name", "") == "haversine":
-        res, stats = batched_trips([requests[i] for i in multi], circuity=provider.circuity,
-                                   device=device, improve=[wants_improve(requests[i]) for i in multi],
-                                   exchange=[wants_exchange(requests[i]) for i in multi])
-        trip_map = dict(zip(multi, res))
+        # time-window requests (routing/timewindows.py) ride in the same batch; a malformed one is
+        # left out here and answered with its error by optimize_route below
+        tws = [_tw_or_none(requests[i]) for i in multi]
+        kw = {"time_windows": tws} if any(v is not None for v in tws) else {}
+        got = batched_trips([requests[i] for i in multi], circuity=provider.circuity,
+                            device=device, improve=[wants_improve(requests[i]) for i in multi],
+                            exchange=[wants_exchange(requests[i]) for i in multi], **kw)
+        res, stats = got[0], got[1]
+        # a malformed time-window request keeps no trips: optimize_route answers with its error
+        trip_map = {i: t for i, t in zip(multi, res) if not _tw_malformed(requests[i])}
         stat_map = dict(zip(multi, stats))
+        if kw:
+            tw_map = dict(zip(multi, got[2]))
     out = []
     for i, r in enumerate(requests):
         t = trip_map.get(i)
         if isinstance(t, InfeasibleStops):
             out.append({"error": str(t)})
             continue
-        out.append(optimize_route(r, provider, engine, trips=t, improvement=stat_map.get(i)))
+        out.append(optimize_route(r, provider, engine, trips=t, improvement=stat_map.get(i),
+                                  tw_result=tw_map.get(i)))
     return out
+
+
+def _tw_or_none(request):
+    if not wants_time_windows(request):
+        return None
+    try:
+        return parse_time_windows(request)
+    except ValueError:
+        return None
+
+
+def _tw_malformed(request) -> bool:
+    return wants_time_windows(request) and _tw_or_none(request) is None

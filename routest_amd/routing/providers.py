@@ -113,6 +113,12 @@ class HaversineProvider:
         return haversine_matrix([p["lat"] for p in points], [p["lon"] for p in points],
                                 self.circuity)
 
+    def time_matrix(self, points: List[Dict[str, float]], profile: str, ctx=None):
+        """``(seconds, metres)`` for time-window planning (routing/timewindows.py): the metres of
+        :meth:`matrix`, each divided once in float64 by the profile's speed."""
+        metres = np.asarray(self.matrix(points, profile), dtype=np.float64)
+        return metres / PROFILE_SPEED_MPS.get(profile, PROFILE_SPEED_MPS["driving-car"]), metres
+
     def directions(self, coords: List[List[float]], profile: str) -> Dict[str, Any]:
         """coords: [[lon, lat], ...] -> ORS-shaped GeoJSON Feature."""
         maybe_fail("provider_timeout")
@@ -197,6 +203,10 @@ class ORSProvider:
         if not dm:
             raise ProviderError("ORS matrix returned no distances")
         return np.asarray(dm, dtype=np.float64)
+
+    def time_matrix(self, points: List[Dict[str, float]], profile: str, ctx=None):
+        from .timewindows import NEEDS_MATRIX_TIMES
+        raise ProviderError(NEEDS_MATRIX_TIMES)
 
     def directions(self, coords: List[List[float]], profile: str) -> Dict[str, Any]:
         import requests

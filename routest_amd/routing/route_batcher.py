@@ -40,7 +40,7 @@ from .batched import batched_trips
 from .greedy import InfeasibleStops
 from .exchange import wants_exchange
 from .improve import wants_improve
-from .optimizer import optimize_route
+from .optimizer import _tw_or_none, optimize_route
 from .providers import ProviderError
 
 log = get_logger("route_batcher")
@@ -71,6 +71,9 @@ class _LegView:
 
     def matrix(self, points, profile, **kw):
         return self.base.matrix(points, profile, **kw)
+
+    def time_matrix(self, points, profile, **kw):
+        return self.base.time_matrix(points, profile, **kw)
 
     def _key(self, ctx) -> Optional[int]:
         if not hasattr(self.base, "metric_key"):
@@ -161,15 +164,17 @@ class RouteBatcher:
         more contexts than the metric cache holds never loses one in between.  Requests that ask
         for ``improve`` / ``exchange`` get their trips improved right after K6 (K6b, K6c), before the
         legs.  Returns
-        (trips by request, legs dict, host edge costs by metric key, improvement stats by request)."""
+        (trips by request, legs dict, host edge costs by metric key, improvement stats by request,
+        time-window schedules by request)."""
         prov = self.provider
         trips: Dict[int, Any] = {}
         stats: Dict[int, Any] = {}
+        tws: Dict[int, Any] = {}
         legs: Dict[tuple, tuple] = {}
         host_costs: Dict[int, np.ndarray] = {}
         valid = [k for k, r in enumerate(payloads) if _valid_points(r) and not isinstance(ctxs[k], ProviderError)]
         if not valid:
-            return trips, legs, host_costs, stats
+            return trips, legs, host_costs, stats, tws
         groups: Dict[Any, List[int]] = {}
         first: Dict[Any, Any] = {}
         for k in valid:
@@ -180,16 +185,16 @@ class RouteBatcher:
         for gk, ks in groups.items():
             try:
                 with prov.pinned_metric(first[gk], device) as key:
-                    self._plan_group(payloads, ks, key, device, trips, legs, stats)
+                    self._plan_group(payloads, ks, key, device, trips, legs, stats, tws)
                     if getattr(prov, "_steps", None) is not None:
                         host_costs[key] = prov.edge_seconds(key, device)
             except ValueError as e:
                 if first[gk] is None or first[gk].avoid is None:
                     raise
                 trips.update({k: ProviderError(str(e)) for k in ks})
-        return trips, legs, host_costs, stats
+        return trips, legs, host_costs, stats, tws
 
-    def _plan_group(self, payloads, ks, key, device, trips, legs, stats) -> None:
+    def _plan_group(self, payloads, ks, key, device, trips, legs, stats, tws) -> None:
         prov = self.provider
         pts = {k: [payloads[k]["source_point"]] + list(payloads[k]["destination_points"]) for k in ks}
         flat = np.array([[p["lon"], p["lat"]] for k in ks for p in pts[k]], dtype=np.float64)
@@ -204,14 +209,22 @@ class RouteBatcher:
             mats = prov.router(device).matrices([nodes[k].tolist() for k in multi], key)
             nm = max(len(pts[k]) for k in multi)
             D = np.zeros((len(multi), nm, nm))
-            for i, (k, (_, met)) in enumerate(zip(multi, mats)):
+            # time-window requests (routing/timewindows.py) are planned on the seconds as well
+            tw = [_tw_or_none(payloads[k]) for k in multi]
+            T = np.zeros((len(multi), nm, nm)) if any(v is not None for v in tw) else None
+            for i, (k, (sec, met)) in enumerate(zip(multi, mats)):
                 n = len(pts[k])
                 D[i, :n, :n] = met
-            res, st = batched_trips([payloads[k] for k in multi], device=device, D=D,
-                                    improve=[wants_improve(payloads[k]) for k in multi],
-                                    exchange=[wants_exchange(payloads[k]) for k in multi])
-            trips.update(zip(multi, res))
-            stats.update(zip(multi, st))
+                if T is not None:
+                    T[i, :n, :n] = sec
+            kw = {"time_windows": tw, "T": T} if T is not None else {}
+            got = batched_trips([payloads[k] for k in multi], device=device, D=D,
+                                improve=[wants_improve(payloads[k]) for k in multi],
+                                exchange=[wants_exchange(payloads[k]) for k in multi], **kw)
+            trips.update(zip(multi, got[0]))
+            stats.update(zip(multi, got[1]))
+            if T is not None:
+                tws.update(zip(multi, got[2]))
         pairs = set()
         for k in ks:
             if len(pts[k]) == 2:
@@ -264,41 +277,55 @@ class RouteBatcher:
 
     def plan_batch(self, payloads: Sequence[Any], device=None) -> List[tuple]:
         """The GPU phases of a flush: per request ``(trips or InfeasibleStops or None, view, ctx,
-        improvement stats or None)``."""
+        improvement stats or None)``, with the ``(schedule, statistics)`` of a time-window request
+        as a fifth entry."""
         payloads = list(payloads)
         name = getattr(self.provider, "name", "")
         trips: Dict[int, Any] = {}
         stats: Dict[int, Any] = {}
+        tws: Dict[int, Any] = {}
         view = self.provider
+
+        def plan(k, *four):
+            return four if tws.get(k) is None else four + (tws[k],)
         if name == "graph" and getattr(self.provider, "engine", "astar") != "astar":
             ctxs = self._contexts(payloads)
             try:
-                trips, legs, hc, stats = self._graph_plan(payloads, device, ctxs)
+                trips, legs, hc, stats, tws = self._graph_plan(payloads, device, ctxs)
             except ProviderError as e:
                 return [(e, None, None, None) for _ in payloads]
             view = _LegView(self.provider, legs, device, hc)
             return [(ctxs[k], None, None, None) if isinstance(ctxs[k], ProviderError) else
-                    (trips.get(k), view, ctxs[k], stats.get(k)) for k in range(len(payloads))]
+                    plan(k, trips.get(k), view, ctxs[k], stats.get(k)) for k in range(len(payloads))]
         multi = [k for k, r in enumerate(payloads) if _valid_points(r) and len(r["destination_points"]) > 1]
         if multi and name in ("haversine", "graph"):
-            res, st = batched_trips([payloads[k] for k in multi], circuity=self.provider.circuity,
-                                    device=device, improve=[wants_improve(payloads[k]) for k in multi],
-                                    exchange=[wants_exchange(payloads[k]) for k in multi])
-            trips = dict(zip(multi, res))
-            stats = dict(zip(multi, st))
+            # the haversine flush plans time-window requests too; the A* engine has no seconds
+            # matrix, so there optimize_route answers them with its error
+            tw = [_tw_or_none(payloads[k]) if name == "haversine" else None for k in multi]
+            kw = {"time_windows": tw} if any(v is not None for v in tw) else {}
+            got = batched_trips([payloads[k] for k in multi], circuity=self.provider.circuity,
+                                device=device, improve=[wants_improve(payloads[k]) for k in multi],
+                                exchange=[wants_exchange(payloads[k]) for k in multi], **kw)
+            trips = dict(zip(multi, got[0]))
+            stats = dict(zip(multi, got[1]))
+            if kw:
+                tws = dict(zip(multi, got[2]))
         if name == "graph":
             try:
                 view = _LegView(self.provider, self._graph_legs(payloads, trips, device), device)
             except ProviderError as e:
                 return [(e, None, None, None) for _ in payloads]
-        return [(trips.get(k), view, None, stats.get(k)) for k in range(len(payloads))]
+        return [plan(k, trips.get(k), view, None, stats.get(k)) for k in range(len(payloads))]
 
     def assemble(self, payload: Any, plan: tuple) -> Dict[str, Any]:
         """Host side of one request: GeoJSON Feature (or error) from its planned trips/legs, under
         the routing context it was planned with."""
-        t, view, ctx, improvement = plan
+        t, view, ctx, improvement = plan[:4]
         if isinstance(t, (InfeasibleStops, ProviderError)):
             return {"error": str(t)}
+        if len(plan) > 4:
+            return optimize_route(payload, view, self.engine, trips=t, ctx=ctx, improvement=improvement,
+                                  tw_result=plan[4])
         return optimize_route(payload, view, self.engine, trips=t, ctx=ctx, improvement=improvement)
 
     def run_batch(self, payloads: Sequence[Any], device=None) -> List[Dict[str, Any]]:
