@@ -592,6 +592,48 @@ std::vector<torch::Tensor> route_tw_trips(torch::Tensor D, torch::Tensor T, torc
   return {visit, trip_of, ntrips, status, arrival, start, stats};
 }
 
+// K6e on K6d's own outputs: visit / trip_of / ntrips / arrival / start are rewritten in place for
+// rows with flag != 0 and status == 0 (routing/tw_improve.py).  Returns stats i64 [R,7] = moves,
+// rejected, trips_before, trips_after, len_before_q, len_after_q, waiting_q (0 for rows left alone).
+torch::Tensor route_tw_improve(torch::Tensor D, torch::Tensor T, torch::Tensor npts, torch::Tensor demand,
+                               torch::Tensor cap, torch::Tensor maxd, torch::Tensor open, torch::Tensor close,
+                               torch::Tensor service, torch::Tensor visit, torch::Tensor trip_of,
+                               torch::Tensor ntrips, torch::Tensor status, torch::Tensor arrival,
+                               torch::Tensor start, torch::Tensor flag) {
+  for (auto* t : {&D, &T, &npts, &demand, &cap, &maxd, &open, &close, &service, &visit, &trip_of, &ntrips, &status,
+                  &arrival, &start, &flag})
+    check_dev(*t, "route tensor");
+  TORCH_CHECK(D.scalar_type() == torch::kFloat64 && D.dim() == 3 && D.size(1) == D.size(2),
+              "D must be f64 [R,NM,NM]");
+  TORCH_CHECK(T.scalar_type() == torch::kFloat64 && T.sizes() == D.sizes(), "T must be f64 [R,NM,NM]");
+  const int R = (int)D.size(0), NM = (int)D.size(1);
+  TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
+  TORCH_CHECK(npts.scalar_type() == torch::kInt32 && npts.numel() == R, "npts must be i32 [R]");
+  TORCH_CHECK(demand.scalar_type() == torch::kFloat64 && demand.numel() == (int64_t)R * NM,
+              "demand must be f64 [R,NM]");
+  TORCH_CHECK(cap.scalar_type() == torch::kFloat64 && cap.numel() == R, "cap must be f64 [R]");
+  TORCH_CHECK(maxd.scalar_type() == torch::kFloat64 && maxd.numel() == R, "maxd must be f64 [R]");
+  for (auto* t : {&open, &close, &service, &arrival, &start})
+    TORCH_CHECK(t->scalar_type() == torch::kInt64 && t->numel() == (int64_t)R * NM,
+                "open, close, service, arrival and start must be i64 [R,NM] (milliseconds)");
+  for (auto* t : {&visit, &trip_of})
+    TORCH_CHECK(t->scalar_type() == torch::kInt32 && t->numel() == (int64_t)R * NM,
+                "visit and trip_of must be i32 [R,NM]");
+  TORCH_CHECK(ntrips.scalar_type() == torch::kInt32 && ntrips.numel() == R, "ntrips must be i32 [R]");
+  TORCH_CHECK(status.scalar_type() == torch::kInt32 && status.numel() == R, "status must be i32 [R]");
+  TORCH_CHECK(flag.scalar_type() == torch::kUInt8 && flag.numel() == R, "flag must be u8 [R]");
+  const c10::DeviceGuard guard(D.device());
+  auto stats = torch::zeros({R, 7}, D.options().dtype(torch::kInt64));
+  RT_CHECK_HIP(rt::launch_tw_improve(
+      D.data_ptr<double>(), T.data_ptr<double>(), npts.data_ptr<int>(), demand.data_ptr<double>(),
+      cap.data_ptr<double>(), maxd.data_ptr<double>(), (const long long*)open.data_ptr<int64_t>(),
+      (const long long*)close.data_ptr<int64_t>(), (const long long*)service.data_ptr<int64_t>(),
+      flag.data_ptr<uint8_t>(), R, NM, visit.data_ptr<int>(), trip_of.data_ptr<int>(), ntrips.data_ptr<int>(),
+      status.data_ptr<int>(), (long long*)arrival.data_ptr<int64_t>(), (long long*)start.data_ptr<int64_t>(),
+      (long long*)stats.data_ptr<int64_t>(), cur_stream(D)));
+  return stats;
+}
+
 // K10 candidates: (cand i32 [P,k], cand_d2 i64 [P,k], n_cand i32 [P]) of the fixes (py, px) on the
 // graph's bucket grid (routing/mapmatch.py build_grid).
 std::vector<torch::Tensor> mm_candidates(torch::Tensor start, torch::Tensor items, torch::Tensor nqy,
@@ -1603,6 +1645,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K6d: cheapest-insertion trips under time windows and service times for the flagged rows",
         py::arg("D"), py::arg("T"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"),
         py::arg("open"), py::arg("close"), py::arg("service"), py::arg("flag"));
+  m.def("route_tw_improve", &route_tw_improve,
+        "K6e: window-aware relocate / swap on K6d's outputs (rewritten in place); returns stats [R,7]",
+        py::arg("D"), py::arg("T"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"),
+        py::arg("open"), py::arg("close"), py::arg("service"), py::arg("visit"), py::arg("trip_of"),
+        py::arg("ntrips"), py::arg("status"), py::arg("arrival"), py::arg("start"), py::arg("flag"));
   m.def("route_exchange_trips", &route_exchange_trips,
         "K6c: inter-trip relocate / swap on K6's outputs (visit, trip_of, ntrips rewritten in place)",
         py::arg("D"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"), py::arg("visit"),

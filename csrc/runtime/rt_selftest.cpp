@@ -453,6 +453,99 @@ static void fuzz_tw(std::mt19937_64& rng, int iters) {
   }
 }
 
+// route_core.h tw_improve_trips on tw_trips' output (instances as in fuzz_tw, half as many): every
+// kept trip re-simulates as feasible on usable entries with the reported arrivals / starts, both
+// float walks hold, no stop is lost or repeated, the length never grows, the statistics are the
+// measured ones, and a search that ended on its own leaves nothing for a second run
+static void fuzz_tw_improve(std::mt19937_64& rng, int iters) {
+  for (int it = 0; it < iters / 200; ++it) {
+    const int n1 = 2 + (int)(rng() % 33);
+    std::vector<double> d((size_t)n1 * n1, 0.0), t((size_t)n1 * n1, 0.0), dem(n1, 0.0);
+    for (int a = 0; a < n1; ++a)
+      for (int b = 0; b < n1; ++b)
+        if (a != b) {
+          d[(size_t)a * n1 + b] = 100.0 + (double)(rng() % 1000000) / 37.0;
+          t[(size_t)a * n1 + b] = 10.0 + (double)(rng() % 100000) / 53.0;
+        }
+    if (rng() % 3 == 0 && n1 > 4) {
+      const double bad[6] = {NAN, INFINITY, -5.0, 2147483.647, 3e9, 1e300};
+      for (int x = 0; x < 6; ++x) {
+        std::vector<double>& m = rng() % 2 ? d : t;
+        const int a = 1 + (int)(rng() % (n1 - 1)), b = 1 + (int)(rng() % (n1 - 1));
+        if (a != b) m[(size_t)a * n1 + b] = bad[rng() % 6];
+      }
+    }
+    std::vector<long long> open(n1, 0), close(n1, rtr::kExchangeUnbounded), sv(n1, 0);
+    for (int s = 1; s < n1; ++s) {
+      dem[s] = rng() % 8 == 0 ? 0.1 : (double)(1 + rng() % 3);
+      if (rng() % 10 < 6) {
+        open[s] = (long long)(rng() % 20000000);
+        close[s] = open[s] + (long long)(rng() % 3 == 0 ? 0 : rng() % 8000000);
+        if (rng() % 4 == 0) open[s] = 0;
+      }
+      if (rng() % 2) sv[s] = (long long)(rng() % 600000);
+    }
+    if (rng() % 32 == 0) dem[1 + rng() % (n1 - 1)] = -1.0;
+    const bool free_run = rng() % 3 == 0;
+    const double cap = free_run ? 9e12 : (double)(3 + rng() % 30) + (rng() % 4 == 0 ? 0.3 : 0.0);
+    const double maxd = free_run ? 9e12 : 60000.0 + (double)(rng() % 400000);
+    std::vector<std::vector<int>> trips;
+    std::vector<std::vector<long long>> arr, sta;
+    std::vector<int> bad;
+    rtr::TwStats st0;
+    if (!rtr::tw_trips(d, t, n1, dem, cap, maxd, open, close, sv, trips, arr, sta, bad, st0)) continue;
+    const std::vector<std::vector<int>> before = trips;
+    const rtr::TwImproveStats st = rtr::tw_improve_trips(d, t, n1, dem, cap, maxd, open, close, sv, trips, arr, sta);
+    std::vector<int> seen(n1, 0);
+    long long len = 0, waiting = 0;
+    CHECK(trips.size() == arr.size() && trips.size() == sta.size(), "tw_improve_trips schedule count");
+    for (size_t k = 0; k < trips.size(); ++k) {
+      const std::vector<int>& tr = trips[k];
+      CHECK(tr.size() >= 3 && tr.front() == 0 && tr.back() == 0, "tw_improve_trips broke a trip's ends");
+      CHECK(arr[k].size() + 2 == tr.size() && sta[k].size() + 2 == tr.size(), "tw_improve_trips schedule length");
+      long long clock = 0;
+      bool ok = true;
+      for (size_t p = 0; p + 1 < tr.size(); ++p) {
+        const int a = tr[p], b = tr[p + 1];
+        if (a < 0 || a >= n1 || b < 0 || b >= n1) { ok = false; break; }
+        const long long q = rtr::tw_q(d[(size_t)a * n1 + b]), qt = rtr::tw_q(t[(size_t)a * n1 + b]);
+        ok = ok && q < rtr::kImproveBig && qt < rtr::kImproveBig;
+        len += q;
+        if (b == 0) break;
+        ++seen[b];
+        const long long ar = clock + qt, s0 = std::max(ar, open[b]);
+        ok = ok && s0 <= close[b] && p < arr[k].size() && arr[k][p] == ar && sta[k][p] == s0;
+        waiting += s0 - ar;
+        clock = s0 + sv[b];
+      }
+      CHECK(ok, "tw_improve_trips kept a trip that does not re-simulate as feasible");
+      double s = 0.0, load = 0.0;
+      const int kk = (int)tr.size() - 2;
+      for (int p = 0; p < kk; ++p) s += d[(size_t)tr[p] * n1 + tr[p + 1]];
+      for (int p = 1; p <= kk; ++p) load += dem[tr[p]];
+      CHECK(s + d[(size_t)tr[kk] * n1] <= maxd && load <= cap, "tw_improve_trips kept a trip that fails the float walks");
+    }
+    bool once = true;
+    for (int s = 1; s < n1; ++s) once = once && seen[s] == 1;
+    CHECK(once, "tw_improve_trips lost or repeated a stop");
+    CHECK(st.trips_before == (long long)before.size() && st.trips_after == (long long)trips.size() &&
+              st.trips_after <= st.trips_before && st.len_before_q == st0.len_q,
+          "tw_improve_trips trip counts: %lld -> %lld, %zu -> %zu", st.trips_before, st.trips_after, before.size(), trips.size());
+    CHECK(len == st.len_after_q && st.len_after_q <= st.len_before_q && waiting == st.waiting_q,
+          "tw_improve_trips: length after %lld, measured %lld, before %lld; waiting %lld / %lld", st.len_after_q, len,
+          st.len_before_q, st.waiting_q, waiting);
+    CHECK(st.moves >= 0 && st.moves <= 4LL * (n1 - 1) && (st.rejected == 0 || st.rejected == 1), "tw_improve_trips move count");
+    CHECK(st.moves > 0 || trips == before, "tw_improve_trips changed trips without a move");
+    CHECK(st.moves == 0 || st.len_after_q < st.len_before_q, "tw_improve_trips: moves without a shorter length");
+    if (st.rejected == 0 && st.moves < 4LL * (n1 - 1)) {
+      std::vector<std::vector<int>> again = trips;
+      std::vector<std::vector<long long>> arr2, sta2;
+      const rtr::TwImproveStats st2 = rtr::tw_improve_trips(d, t, n1, dem, cap, maxd, open, close, sv, again, arr2, sta2);
+      CHECK(st2.moves == 0 && again == trips && arr2 == arr && sta2 == sta, "tw_improve_trips left %lld moves", st2.moves);
+    }
+  }
+}
+
 // map_match.h mm_candidates: on random node sets (clusters, duplicates, one line) and fixes inside,
 // on and far outside the grid the answer equals a scan of all nodes sorted by (d2, node id)
 static void fuzz_mm_candidates(std::mt19937_64& rng, int iters) {
@@ -961,6 +1054,7 @@ int main(int argc, char** argv) {
   fuzz_mm_candidates(rng, iters);
   fuzz_mm_viterbi(rng, iters);
   fuzz_avoid_mask(rng, iters);
+  fuzz_tw_improve(rng, iters);
   store_while_reading();
   threaded_pack_format(20000);
   std::printf("rt_selftest: %d iterations, %d failures\n", iters, g_fail);

@@ -10,7 +10,8 @@ launch, K6b, on K6's own tensors) and the call returns ``(results, stats)``, ``s
 request's improvement statistics or ``None``.  Per-request ``exchange`` flags add the inter-trip
 relocate / swap search of :mod:`routing.exchange` between two such passes (on a GPU K6b, K6c, K6b).
 Requests given ``time_windows`` are planned by the cheapest insertion of :mod:`routing.timewindows`
-instead (on a GPU one launch, K6d, over the flagged rows only).
+instead (on a GPU one launch, K6d, over the flagged rows only); per-request ``tw_improve`` flags add
+the window-aware local search of :mod:`routing.tw_improve` on those rows (on a GPU one more launch, K6e).
 Sharding over several GPUs is done by
 :class:`routing.route_batcher.RouteBatcher` (one worker thread per device, no collective).
 """
@@ -27,6 +28,7 @@ from .exchange import UNBOUNDED, improve_exchange_trips
 from .improve import improve_trips
 from .providers import haversine_matrix
 from .timewindows import MAX_STOPS as TW_MAX_STOPS, tw_trips
+from .tw_improve import STAT_KEYS as TWI_STAT_KEYS, tw_improve_trips
 
 TripsOrError = Union[List[List[int]], InfeasibleStops]
 
@@ -127,16 +129,23 @@ def pack_time_windows(requests: Sequence[Dict[str, Any]], time_windows: Sequence
     return op, cl, sv, flags, speed
 
 
-def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw):
-    """K6d over the flagged rows: ``{row: trips or InfeasibleStops}``, ``{row: (schedule, stats)}``."""
+def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw, twi=None):
+    """K6d over the flagged rows: ``{row: trips or InfeasibleStops}``, ``{row: (schedule, stats)}``.
+    ``twi``: uint8 flags of the rows whose trips K6e then improves (``stats["search"]``)."""
     op, cl, sv, twf, speed = tw
     if T is None:
         # one IEEE division per entry, as HaversineProvider.time_matrix does it on the host
         T = D / t(speed).reshape(-1, 1, 1)
     else:
         T = t(np.ascontiguousarray(T, dtype=np.float64))
-    out = C.route_tw_trips(D, T.contiguous(), npts_t, dem_t, cap_t, maxd_t, t(op, torch.int64),
-                           t(cl, torch.int64), t(sv, torch.int64), t(twf, torch.uint8))
+    T = T.contiguous()
+    op_t, cl_t, sv_t = t(op, torch.int64), t(cl, torch.int64), t(sv, torch.int64)
+    out = C.route_tw_trips(D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, t(twf, torch.uint8))
+    search = None
+    if twi is not None and (twi & twf).any():
+        # K6e rewrites K6d's outputs in place for the asking rows; K6d's own statistics stay
+        search = C.route_tw_improve(D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, *out[:6],
+                                    t(twi & twf, torch.uint8)).cpu().numpy()
     visit, trip_of, ntrips, status, arr, start, stats = (c.cpu().numpy() for c in out)
     rows = np.flatnonzero(twf)
     if (status[rows] > 1).any():
@@ -155,12 +164,15 @@ def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw):
             p += len(trip) - 2
         sched[k] = (one, {"insertions": int(stats[k, 0]), "rejected": int(stats[k, 1]), "trips": len(trips[x]),
                           "len_q": int(stats[k, 2]), "waiting_q": int(stats[k, 3])})
+        if search is not None and twi[k]:
+            sched[k][1]["search"] = {key: int(v) for key, v in zip(TWI_STAT_KEYS, search[k])}
     return res, sched
 
 
 def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device,
                          D: Optional[np.ndarray] = None, improve: Optional[Sequence[Any]] = None,
-                         exchange: Optional[Sequence[Any]] = None, tw=None, T: Optional[np.ndarray] = None):
+                         exchange: Optional[Sequence[Any]] = None, tw=None, T: Optional[np.ndarray] = None,
+                         tw_improve: Optional[Sequence[Any]] = None):
     # K6 indexes its LDS order / visited arrays by stop number: a request longer than the padded
     # width would write past them, so it is refused here, before anything reaches the device
     nm = int(D.shape[1]) if D is not None else int(np.shape(lat)[1])
@@ -201,7 +213,8 @@ def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device
         # K6d plans the flagged rows (a batch nobody flags launches nothing); the others keep K6's
         twres: List[Any] = [None] * len(n)
         if tw[3].any():
-            planned, sched = _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw)
+            planned, sched = _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw,
+                                        _flags(tw_improve, len(n)))
             for k, v in planned.items():
                 out[k] = v
                 twres[k] = sched.get(k)
@@ -228,9 +241,11 @@ def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device
 
 def batched_trips_cpu(lat, lon, dem, npts, cap, maxd, circuity: float,
                       D: Optional[np.ndarray] = None, improve: Optional[Sequence[Any]] = None,
-                      exchange: Optional[Sequence[Any]] = None, tw=None, T: Optional[np.ndarray] = None):
+                      exchange: Optional[Sequence[Any]] = None, tw=None, T: Optional[np.ndarray] = None,
+                      tw_improve: Optional[Sequence[Any]] = None):
     out: List[TripsOrError] = []
     flags, xflags = _both_flags(improve, exchange, len(npts))
+    twi = _flags(tw_improve, len(npts))
     stats: List[Optional[Dict[str, int]]] = []
     twres: List[Any] = []
     for k in range(len(npts)):
@@ -243,6 +258,11 @@ def batched_trips_cpu(lat, lon, dem, npts, cap, maxd, circuity: float,
             try:
                 trips, sched, tst = tw_trips(d, sec, dem[k, :n].tolist(), float(cap[k]), float(maxd[k]),
                                              tw[0][k, :n], tw[1][k, :n], tw[2][k, :n])
+                if twi is not None and twi[k]:
+                    # the reference of K6e (routing/tw_improve.py) on the insertion's trips
+                    trips, sched, search = tw_improve_trips(d, sec, trips, dem[k, :n].tolist(), float(cap[k]),
+                                                            float(maxd[k]), tw[0][k, :n], tw[1][k, :n], tw[2][k, :n])
+                    tst = dict(tst, trips=len(trips), search=search)
                 out.append(trips)
                 twres.append((sched, tst))
             except InfeasibleStops as e:
@@ -271,7 +291,8 @@ def batched_trips(requests: Sequence[Dict[str, Any]], circuity: float = 1.3,
                   device: Optional[Any] = None, D: Optional[np.ndarray] = None,
                   improve: Optional[Sequence[Any]] = None,
                   exchange: Optional[Sequence[Any]] = None,
-                  time_windows: Optional[Sequence[Any]] = None, T: Optional[np.ndarray] = None):
+                  time_windows: Optional[Sequence[Any]] = None, T: Optional[np.ndarray] = None,
+                  tw_improve: Optional[Sequence[Any]] = None):
     """``D``: given distance matrices [R, nm, nm] (road metres from the CCH router) instead of the
     haversine K5.  ``improve`` / ``exchange``: one flag per request; when either is given, returns
     ``(results, stats)``.  ``exchange`` implies ``improve`` (:mod:`routing.exchange`).
@@ -281,7 +302,11 @@ def batched_trips(requests: Sequence[Dict[str, Any]], circuity: float = 1.3,
     :mod:`routing.timewindows` (on a GPU one launch, K6d) and ignore ``improve`` / ``exchange``, the
     others are planned as without the argument.  ``T``: the seconds matrices that go with ``D``
     (without ``D``: haversine metres over the request profile's speed).  When given, the call
-    returns ``(results, stats, tw)`` with ``tw[k]`` None or ``(schedule, statistics)``."""
+    returns ``(results, stats, tw)`` with ``tw[k]`` None or ``(schedule, statistics)``.
+
+    ``tw_improve``: one flag per request, honoured only on time-window rows: their trips are improved
+    by the window-aware local search of :mod:`routing.tw_improve` (on a GPU one more launch, K6e) and
+    ``statistics["search"]`` holds what it did; an unflagged row's entry is as without the argument."""
     if time_windows is not None and (D is None) != (T is None):
         raise ValueError("time windows on given matrices need both D (metres) and T (seconds)")
     if not requests:
@@ -295,5 +320,6 @@ def batched_trips(requests: Sequence[Dict[str, Any]], circuity: float = 1.3,
         tw = pack_time_windows(requests, time_windows, nm)
     if device is not None and torch.device(device).type == "cuda":
         return batched_trips_device(*packed, circuity=circuity, device=device, D=D, improve=improve,
-                                    exchange=exchange, tw=tw, T=T)
-    return batched_trips_cpu(*packed, circuity=circuity, D=D, improve=improve, exchange=exchange, tw=tw, T=T)
+                                    exchange=exchange, tw=tw, T=T, tw_improve=tw_improve)
+    return batched_trips_cpu(*packed, circuity=circuity, D=D, improve=improve, exchange=exchange, tw=tw, T=T,
+                             tw_improve=tw_improve)

@@ -20,6 +20,8 @@ are routed, and ``properties.improvement`` reports what it did.  Single-destinat
 ``alternatives`` requests ignore the field; without it every response is unchanged.
 ``"exchange": true`` (same rule; it implies ``improve``) adds the inter-trip relocate / swap search
 of :mod:`routing.exchange` between two such passes; the answer may then hold fewer trips.
+``"tw_improve": true`` (same rule) on a time-window request improves the cheapest insertion's trips
+by the window-aware local search of :mod:`routing.tw_improve`; any other request ignores it.
 The batched GPU path for many concurrent requests (K5 + K6) is :func:`optimize_many`.
 """
 from __future__ import annotations
@@ -34,6 +36,7 @@ from .improve import improve_trips, improvement_properties, wants_improve
 from .providers import ProviderError, _bbox, profile_for
 from .timewindows import (NEEDS_MATRIX_TIMES, parse_time_windows, schedule_properties, tw_trips,
                           wants_time_windows)
+from .tw_improve import tw_improve_trips, wants_tw_improve
 
 
 def _annotate(feature: Dict[str, Any], driver: Dict[str, Any], vehicle_type: str, engine: str) -> None:
@@ -116,13 +119,14 @@ def assemble_trips(provider, all_points: List[Dict[str, Any]], trips: List[List[
 def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, Any],
                trips: Optional[List[List[int]]] = None, ctx=None, improve: bool = False,
                improvement: Optional[Dict[str, int]] = None, exchange: bool = False,
-               tw=None, tw_result=None) -> Dict[str, Any]:
+               tw=None, tw_result=None, tw_improve: bool = False) -> Dict[str, Any]:
     """``improve``: re-sequence the trips built here (routing/improve.py); ``exchange``: also move
     stops between them (routing/exchange.py; it implies ``improve``).  Trips given by the caller
     are taken as they are; ``improvement`` holds their statistics if they were improved.
     ``tw``: the request's ``(open_q, close_q, sv_q)`` (routing/timewindows.py): the trips are built
     by cheapest insertion under the windows, ``improve`` / ``exchange`` are ignored and the response
-    carries ``schedule`` / ``time_windows``; ``tw_result``: the ``(schedule, statistics)`` of given trips."""
+    carries ``schedule`` / ``time_windows``; ``tw_result``: the ``(schedule, statistics)`` of given trips.
+    ``tw_improve``: the trips built here under the windows are improved (routing/tw_improve.py)."""
     all_points = [source] + list(destinations)
     if tw is not None and tw_result is None:
         # (trips that come without their schedule were not planned under the windows)
@@ -138,6 +142,11 @@ def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, A
                                                _float(driver.get("maximum_distance", 9e12), 9e12), *tw)
         except InfeasibleStops as e:
             return {"error": str(e)}
+        if tw_improve:
+            trips, schedule, search = tw_improve_trips(
+                d, sec, trips, demand, _float(driver.get("vehicle_capacity", 9e12), 9e12),
+                _float(driver.get("maximum_distance", 9e12), 9e12), *tw)
+            tstats = dict(tstats, trips=len(trips), search=search)
         tw_result = (schedule, tstats)
     if tw is not None:
         feature = assemble_trips(provider, all_points, trips, profile, source, destinations, ctx)
@@ -232,7 +241,8 @@ def _optimize(input_data, provider, engine, trips, ctx, improvement, driver, veh
             return {"error": str(e)}
     feature = multi_stop(provider, source, destinations, profile, driver, trips, ctx,
                          improve=wants_improve(input_data), improvement=improvement,
-                         exchange=wants_exchange(input_data), tw=tw, tw_result=tw_result)
+                         exchange=wants_exchange(input_data), tw=tw, tw_result=tw_result,
+                         tw_improve=wants_tw_improve(input_data))
     if "error" in feature:
         return feature
     _annotate(feature, driver, vehicle_type, engine)
@@ -255,7 +265,8 @@ def optimize_many(requests: Sequence[Dict[str, Any]], provider, engine: str = "b
         # time-window requests (routing/timewindows.py) ride in the same batch; a malformed one is
         # left out here and answered with its error by optimize_route below
         tws = [_tw_or_none(requests[i]) for i in multi]
-        kw = {"time_windows": tws} if any(v is not None for v in tws) else {}
+        kw = ({"time_windows": tws, "tw_improve": [wants_tw_improve(requests[i]) for i in multi]}
+              if any(v is not None for v in tws) else {})
         got = batched_trips([requests[i] for i in multi], circuity=provider.circuity,
                             device=device, improve=[wants_improve(requests[i]) for i in multi],
                             exchange=[wants_exchange(requests[i]) for i in multi], **kw)

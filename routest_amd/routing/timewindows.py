@@ -285,10 +285,21 @@ def parse_time_windows(payload) -> Tuple[List[int], List[int], List[int]]:
 
 def schedule_properties(schedule: Schedule, stats: Dict[str, int], close_q: Sequence[int]
                         ) -> Tuple[List[List[Dict[str, Any]]], Dict[str, Any]]:
-    """``(properties.schedule, properties.time_windows)`` of a response; seconds."""
+    """``(properties.schedule, properties.time_windows)`` of a response; seconds.  With
+    ``stats["search"]`` (the statistics of :mod:`routing.tw_improve`) the second also reports the
+    local search."""
     out = [[{"destination": s - 1, "arrival": a / 1000.0, "start": b / 1000.0,
              "departure": c / 1000.0, "waiting": (b - a) / 1000.0} for s, a, b, c in trip]
            for trip in schedule]
+    search = stats.get("search")
+    if search is not None:
+        info = {"method": METHOD + "+relocate+swap",
+                "stops_with_windows": sum(1 for c in close_q[1:] if int(c) < UNBOUNDED),
+                "trips": int(search["trips_after"]), "waiting": int(search["waiting_q"]) / 1000.0,
+                "moves": int(search["moves"]), "trips_before": int(search["trips_before"]),
+                "matrix_distance_before": int(search["len_before_q"]) / 1000.0,
+                "matrix_distance_after": int(search["len_after_q"]) / 1000.0}
+        return out, info
     info = {"method": METHOD,
             "stops_with_windows": sum(1 for c in close_q[1:] if int(c) < UNBOUNDED),
             "trips": int(stats["trips"]), "waiting": int(stats["waiting_q"]) / 1000.0}
