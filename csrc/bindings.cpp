@@ -698,6 +698,63 @@ std::vector<torch::Tensor> mm_viterbi(torch::Tensor cand_d2, torch::Tensor n_can
   return {choice, seg, nseg, cost};
 }
 
+// K10 edge mode candidates: (cand_edge i32 [P,k], cand_d2 i64 [P,k], cand_fq i32 [P,k], n_cand i32
+// [P], n_survivors i32 [P]) of the fixes on the graph's edge grid (routing/mapmatch_edge.py
+// build_edge_grid / pack_records).
+std::vector<torch::Tensor> mm_edge_candidates(torch::Tensor start, torch::Tensor items, torch::Tensor rec, int64_t y0,
+                                              int64_t x0, int64_t cell, int64_t ny, int64_t nx, torch::Tensor py,
+                                              torch::Tensor px, int64_t radius_cm, int64_t k) {
+  for (auto* t : {&start, &items, &rec, &py, &px}) check_dev(*t, "map-matching tensor");
+  const int64_t P = py.numel();
+  TORCH_CHECK(rec.scalar_type() == torch::kInt64 && rec.dim() == 2 && rec.size(1) == 4, "rec must be i64 [E,4]");
+  const int64_t E = rec.size(0);
+  TORCH_CHECK(E >= 1 && E < (1LL << 30), "edge ids must be below 2^30");
+  TORCH_CHECK(cell >= 1 && ny >= 1 && nx >= 1 && ny * nx < (1LL << 31) - 1, "grid shape");
+  TORCH_CHECK(start.scalar_type() == torch::kInt32 && start.numel() == ny * nx + 1, "start must be i32 [ny*nx+1]");
+  TORCH_CHECK(items.scalar_type() == torch::kInt32 && items.numel() < (1LL << 31), "items must be i32");
+  TORCH_CHECK(py.scalar_type() == torch::kInt64 && px.scalar_type() == torch::kInt64 && px.numel() == P,
+              "py / px must be i64 [P]");
+  TORCH_CHECK(P < (1LL << 29), "too many fixes");
+  TORCH_CHECK(k >= 1 && k <= 16, "k must be in 1..16");
+  TORCH_CHECK(radius_cm >= 1 && radius_cm <= 100000, "radius must be in 1..100000 cm");
+  const c10::DeviceGuard guard(py.device());
+  auto iopt = py.options().dtype(torch::kInt32);
+  auto cand = torch::empty({P, k}, iopt);
+  auto cand_d2 = torch::empty({P, k}, py.options());
+  auto cand_fq = torch::empty({P, k}, iopt);
+  auto n_cand = torch::empty({P}, iopt);
+  auto n_surv = torch::empty({P}, iopt);
+  RT_CHECK_HIP(rt::launch_mm_edge_candidates(
+      start.data_ptr<int>(), items.data_ptr<int>(), (int)items.numel(), (const long long*)rec.data_ptr<int64_t>(),
+      (int)E, (long long)y0, (long long)x0, (long long)cell, (int)ny, (int)nx,
+      (const long long*)py.data_ptr<int64_t>(), (const long long*)px.data_ptr<int64_t>(), (int)P, (long long)radius_cm,
+      (int)k, cand.data_ptr<int>(), (long long*)cand_d2.data_ptr<int64_t>(), cand_fq.data_ptr<int>(),
+      n_cand.data_ptr<int>(), n_surv.data_ptr<int>(), cur_stream(py)));
+  return {cand, cand_d2, cand_fq, n_cand, n_surv};
+}
+
+// K10 edge mode: route_cm i64 [rows,K,K] from the matrix rows' metres and the candidates' edge / off / lc.
+torch::Tensor mm_edge_route_cm(torch::Tensor met, torch::Tensor e1, torch::Tensor off1, torch::Tensor lc1,
+                               torch::Tensor e2, torch::Tensor off2) {
+  for (auto* t : {&met, &e1, &off1, &lc1, &e2, &off2}) check_dev(*t, "map-matching tensor");
+  TORCH_CHECK(met.scalar_type() == torch::kFloat32 && met.dim() == 3 && met.size(1) == met.size(2),
+              "met must be f32 [rows,K,K]");
+  const int64_t rows = met.size(0), K = met.size(1);
+  TORCH_CHECK(K >= 1 && K <= 16, "K must be in 1..16");
+  TORCH_CHECK(rows <= (1LL << 30), "too many rows");
+  for (auto* t : {&e1, &e2})
+    TORCH_CHECK(t->scalar_type() == torch::kInt32 && t->numel() == rows * K, "edges must be i32 [rows,K]");
+  for (auto* t : {&off1, &lc1, &off2})
+    TORCH_CHECK(t->scalar_type() == torch::kInt64 && t->numel() == rows * K, "off / lc must be i64 [rows,K]");
+  const c10::DeviceGuard guard(met.device());
+  auto out = torch::empty({rows, K, K}, met.options().dtype(torch::kInt64));
+  RT_CHECK_HIP(rt::launch_mm_edge_route_cm(
+      met.data_ptr<float>(), e1.data_ptr<int>(), (const long long*)off1.data_ptr<int64_t>(),
+      (const long long*)lc1.data_ptr<int64_t>(), e2.data_ptr<int>(), (const long long*)off2.data_ptr<int64_t>(),
+      (long long)rows, (int)K, (long long*)out.data_ptr<int64_t>(), cur_stream(met)));
+  return out;
+}
+
 rt::NormParams norm_from(const std::vector<double>& norm) {
   TORCH_CHECK(norm.size() == 8, "norm must hold 4 scales + 4 shifts");
   rt::NormParams np;
@@ -1661,6 +1718,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mm_viterbi", &mm_viterbi, "K10: segmenting Viterbi of the map matcher over given costs",
         py::arg("cand_d2"), py::arg("n_cand"), py::arg("route_cm"), py::arg("g"), py::arg("npts"),
         py::arg("beta_cm"), py::arg("sigma_cm"), py::arg("max_detour_cm"));
+  m.def("mm_edge_candidates", &mm_edge_candidates, "K10 edge mode: candidates of GPS fixes on the edge grid",
+        py::arg("start"), py::arg("items"), py::arg("rec"), py::arg("y0"), py::arg("x0"), py::arg("cell"),
+        py::arg("ny"), py::arg("nx"), py::arg("py"), py::arg("px"), py::arg("radius_cm"), py::arg("k"));
+  m.def("mm_edge_route_cm", &mm_edge_route_cm, "K10 edge mode: route centimetres between points on edges",
+        py::arg("met"), py::arg("e1"), py::arg("off1"), py::arg("lc1"), py::arg("e2"), py::arg("off2"));
+  m.def("mm_edge_lds_capacity", []() { return (int64_t)rt::mm_edge_lds_capacity(); },
+        "K10 edge mode: survivors of one fix the candidate kernel selects from LDS");
   m.def("big_layer1", &big_layer1, "wide MLP: featurize + layer 1 -> h1 (hperm order)",
         py::arg("records"), py::arg("w1p"), py::arg("H"), py::arg("norm"), py::arg("h1"),
         py::arg("xf") = py::none(), py::arg("mbits") = py::none());

@@ -280,6 +280,23 @@ hipError_t launch_mm_viterbi(const long long* cand_d2, const int* n_cand, const 
                              long long sigma_cm, long long max_detour_cm, int* choice, int* seg, int* nseg,
                              long long* cost, hipStream_t stream);
 
+// ---- K10 edge mode : map_match_edge.hip ----
+// Integer-only (routing/mapmatch_edge.py).  Candidates: per fix the k matchable edges within
+// radius_cm with the smallest (d2 to the projection, edge id) from the edge grid (start
+// [ny*nx+1], items [n_items], records i64 [E, 4] = ay, ax, wy | wx << 32, lc); cand_edge / cand_d2 /
+// cand_fq [P, k] are -1 padded; n_surv [P] counts the in-radius item entries of the covered cells
+// (above mm_edge_lds_capacity() the kernel selects by rescanning instead of from LDS).
+int mm_edge_lds_capacity();
+hipError_t launch_mm_edge_candidates(const int* start, const int* items, int n_items, const long long* rec, int E,
+                                     long long y0, long long x0, long long cell, int ny, int nx, const long long* py,
+                                     const long long* px, int P, long long radius_cm, int k, int* cand_edge,
+                                     long long* cand_d2, int* cand_fq, int* n_cand, int* n_surv, hipStream_t stream);
+// route_cm [rows, K, K] of the steps from the matrix rows' metres (inf / negative / NaN = no route)
+// and the two fixes' candidates (edge -1 = padding, off, lc) [rows, K].
+hipError_t launch_mm_edge_route_cm(const float* met, const int* e1, const long long* off1, const long long* lc1,
+                                   const int* e2, const long long* off2, long long rows, int K, long long* out,
+                                   hipStream_t stream);
+
 // ---- persistent single-request scorer : persistent_serve.hip ----
 struct PersistentScorer;
 PersistentScorer* pscore_create(int device, const void* blob, int H, const NormParams& np, int cap,

@@ -9,7 +9,8 @@
 //  * route_assemble_graph: graph-provider assembly from given trips + searched legs (tests);
 //    `improvement`: the statistics of trips that were improved (routing/improve.py).
 //  * MmGrid / mm_viterbi: the host reference of the map matcher (map_match.h; the definition is in
-//    routing/mapmatch.py, the HIP kernels in csrc/map_match.hip).
+//    routing/mapmatch.py, the HIP kernels in csrc/map_match.hip); MmEdgeGrid / mm_edge_route_cm: the
+//    edge-based matcher's (routing/mapmatch_edge.py, csrc/map_match_edge.hip).
 //  * RouteStore / RowId: the route service's SQLite writer (route_store.h) over requests assembled
 //    by the two functions above (as_row=True) — its CPU tests.
 #include <pybind11/numpy.h>
@@ -120,6 +121,79 @@ class PyMmGrid {
  private:
   rtr::MmGrid g_;
 };
+
+// map_match.h: the bucket grid over a graph's matchable edges and its radius queries
+class PyMmEdgeGrid {
+ public:
+  using I64 = py::array_t<int64_t, py::array::c_style | py::array::forcecast>;
+  using I32 = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
+  PyMmEdgeGrid(I64 qy, I64 qx, I32 tail, I32 head, I64 lc, int64_t cell) {
+    if (qy.ndim() != 1 || qx.ndim() != 1 || qy.shape(0) != qx.shape(0)) throw std::invalid_argument("qy/qx mismatch");
+    if (tail.ndim() != 1 || head.ndim() != 1 || lc.ndim() != 1 || tail.shape(0) != head.shape(0) ||
+        tail.shape(0) != lc.shape(0))
+      throw std::invalid_argument("tail/head/lc mismatch");
+    if (cell < 1) throw std::invalid_argument("cell: at least one centimetre");
+    g_.build(qy.data(), qx.data(), (size_t)qy.shape(0), tail.data(), head.data(), lc.data(), (size_t)tail.shape(0), cell);
+  }
+  py::tuple candidates(I64 py_, I64 px_, int64_t radius_cm, int k) const {
+    if (py_.ndim() != 1 || px_.ndim() != 1 || py_.shape(0) != px_.shape(0)) throw std::invalid_argument("py/px mismatch");
+    if (k < 1 || k > rtr::kMmMaxK) throw std::invalid_argument("k in 1..16");
+    const py::ssize_t P = py_.shape(0);
+    py::array_t<int32_t> cand({P, (py::ssize_t)k}), fq({P, (py::ssize_t)k});
+    py::array_t<int64_t> d2({P, (py::ssize_t)k});
+    py::array_t<int32_t> n(P);
+    {
+      const int64_t* a = py_.data();
+      const int64_t* b = px_.data();
+      int32_t* c = cand.mutable_data();
+      int64_t* d = d2.mutable_data();
+      int32_t* f = fq.mutable_data();
+      int32_t* e = n.mutable_data();
+      py::gil_scoped_release nogil;
+      rtr::mm_edge_candidates(g_, a, b, (size_t)P, radius_cm, k, c, d, f, e);
+    }
+    return py::make_tuple(cand, d2, fq, n);
+  }
+  py::dict layout() const {   // the grid itself, for tests of its listing property
+    py::dict d;
+    d["y0"] = g_.y0;
+    d["x0"] = g_.x0;
+    d["cell"] = g_.cell;
+    d["ny"] = g_.ny;
+    d["nx"] = g_.nx;
+    d["start"] = py::array_t<int32_t>((py::ssize_t)g_.start.size(), g_.start.data());
+    d["items"] = py::array_t<int32_t>((py::ssize_t)g_.items.size(), g_.items.data());
+    return d;
+  }
+
+ private:
+  rtr::MmEdgeGrid g_;
+};
+
+// route_cm i64 [rows, K, K] (map_match.h mm_edge_route_cm)
+py::array_t<int64_t> py_mm_edge_route_cm(py::array_t<float, py::array::c_style | py::array::forcecast> met,
+                                         py::array_t<int32_t, py::array::c_style | py::array::forcecast> e1,
+                                         py::array_t<int64_t, py::array::c_style | py::array::forcecast> off1,
+                                         py::array_t<int64_t, py::array::c_style | py::array::forcecast> lc1,
+                                         py::array_t<int32_t, py::array::c_style | py::array::forcecast> e2,
+                                         py::array_t<int64_t, py::array::c_style | py::array::forcecast> off2) {
+  if (met.ndim() != 3 || met.shape(1) != met.shape(2)) throw std::invalid_argument("met must be [rows, K, K]");
+  const py::ssize_t rows = met.shape(0), K = met.shape(1);
+  if (K < 1 || K > rtr::kMmMaxK) throw std::invalid_argument("K in 1..16");
+  auto row_k = [&](const py::array& a) { return a.ndim() == 2 && a.shape(0) == rows && a.shape(1) == K; };
+  if (!row_k(e1) || !row_k(off1) || !row_k(lc1) || !row_k(e2) || !row_k(off2))
+    throw std::invalid_argument("edge, off and lc must be [rows, K]");
+  py::array_t<int64_t> out({rows, K, K});
+  {
+    const float* m = met.data();
+    const int32_t *a = e1.data(), *b = e2.data();
+    const int64_t *o1 = off1.data(), *l1 = lc1.data(), *o2 = off2.data();
+    int64_t* o = out.mutable_data();
+    py::gil_scoped_release nogil;
+    rtr::mm_edge_route_cm(m, a, o1, l1, b, o2, (size_t)rows, (int)K, o);
+  }
+  return out;
+}
 
 // (choice i32 [B, T], segment i32 [B, T], n_segments i32 [B], cost i64 [B])
 py::tuple py_mm_viterbi(py::array_t<int64_t, py::array::c_style | py::array::forcecast> cand_d2,
@@ -557,6 +631,14 @@ void bind_route(py::module& m) {
           return PyMmGrid(qy, qx).candidates(py_, px_, radius_cm, k);
         },
         py::arg("qy"), py::arg("qx"), py::arg("py"), py::arg("px"), py::arg("radius_cm"), py::arg("k"));
+  py::class_<PyMmEdgeGrid>(m, "MmEdgeGrid")
+      .def(py::init<PyMmEdgeGrid::I64, PyMmEdgeGrid::I64, PyMmEdgeGrid::I32, PyMmEdgeGrid::I32, PyMmEdgeGrid::I64,
+                    int64_t>(),
+           py::arg("qy"), py::arg("qx"), py::arg("tail"), py::arg("head"), py::arg("lc"), py::arg("cell"))
+      .def("candidates", &PyMmEdgeGrid::candidates, py::arg("py"), py::arg("px"), py::arg("radius_cm"), py::arg("k"))
+      .def("layout", &PyMmEdgeGrid::layout);
+  m.def("mm_edge_route_cm", &py_mm_edge_route_cm, py::arg("met"), py::arg("e1"), py::arg("off1"), py::arg("lc1"),
+        py::arg("e2"), py::arg("off2"));
   m.def("mm_viterbi", &py_mm_viterbi, py::arg("cand_d2"), py::arg("n_cand"), py::arg("route_cm"), py::arg("g"),
         py::arg("npts"), py::arg("beta_cm"), py::arg("sigma_cm"), py::arg("max_detour_cm"));
   m.def("route_optimize_cpu", &route_optimize_cpu, py::arg("body"), py::arg("json_ok") = true,

@@ -3,7 +3,7 @@
 // alternatives.h: via-node candidates and scores; route_store.h + history_db.h: the route service's
 // SQLite writer fills a database with fuzzed rows, the native history reads run over it with
 // fuzzed limits / ids, and the two run against each other on two threads; map_match.h: the map
-// matcher's candidate search against a scan and its Viterbi against full enumeration).
+// matcher's node and edge candidate searches against a scan and its Viterbi against full enumeration).
 // Built with -fsanitize=address,undefined by `tools/build_ext.py --sanitize` or the CMake `asan`
 // preset (the reference has no race detection / sanitizers at all), and run by
 // tests/test_sanitize_cpu.py.  Exit code 0 = all invariants held and no sanitizer report.
@@ -22,6 +22,7 @@
 #include <random>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "alternatives.h"
@@ -600,6 +601,91 @@ static void fuzz_mm_candidates(std::mt19937_64& rng, int iters) {
   }
 }
 
+// map_match.h mm_edge_candidates: on random edge sets (short and long edges, zero-length ones, both
+// directions, edges over the span or length limit) under random cell sizes the answer equals a scan
+// of all matchable edges sorted by (d2, edge id), and the projection's distance is the true
+// point-to-segment distance up to the rounding of fq and Q
+static void fuzz_mm_edge_candidates(std::mt19937_64& rng, int iters) {
+  for (int it = 0; it < iters / 200; ++it) {
+    const size_t n = 2 + rng() % 200, E = 1 + rng() % 500;
+    const int64_t span = 1 + (int64_t)(rng() % 3000000), ox = (int64_t)(rng() % 4000000000ULL) - 2000000000LL;
+    std::vector<int64_t> qy(n), qx(n), lc(E);
+    for (size_t i = 0; i < n; ++i) {
+      qy[i] = 162000000 + (int64_t)(rng() % span);
+      qx[i] = ox + (int64_t)(rng() % span);
+    }
+    if (rng() % 4 == 0) {   // two far nodes: edges to them exceed the 2^22 span
+      qy[0] += 5000000;
+      qx[1] -= 4194305;
+    }
+    std::vector<int32_t> tail(E), head(E);
+    for (size_t e = 0; e < E; ++e) {
+      tail[e] = (int32_t)(rng() % n);
+      head[e] = rng() % 16 == 0 ? tail[e] : (int32_t)(rng() % n);   // a zero-length edge now and then
+      if (e && rng() % 8 == 0) {                                     // the other direction of the previous edge
+        tail[e] = head[e - 1];
+        head[e] = tail[e - 1];
+      }
+      lc[e] = rng() % 32 == 0 ? -1 : (rng() % 32 == 0 ? rtr::kMmMaxEdgeLc + 1 : (int64_t)(rng() % 5000000));
+    }
+    rtr::MmEdgeGrid g;
+    g.build(qy.data(), qx.data(), n, tail.data(), head.data(), lc.data(), E, 1 + (int64_t)(rng() % (2 * span)));
+    CHECK(g.ny <= 2049 && g.nx <= 2049 && g.start.back() == (int32_t)g.items.size(), "MmEdgeGrid: %d x %d cells", g.ny,
+          g.nx);
+    const size_t P = 1 + rng() % 30;
+    const int k = 1 + (int)(rng() % 16);
+    const int64_t radius = 1 + (int64_t)(rng() % 100000);
+    std::vector<int64_t> py(P), px(P);
+    for (size_t p = 0; p < P; ++p) {
+      const size_t e = rng() % E;
+      const int64_t t = (int64_t)(rng() % 1001);   // a point along edge e, then moved
+      py[p] = qy[tail[e]] + (qy[head[e]] - qy[tail[e]]) * t / 1000;
+      px[p] = qx[tail[e]] + (qx[head[e]] - qx[tail[e]]) * t / 1000;
+      switch (rng() % 4) {
+        case 0: break;                                                     // on the edge
+        case 1: py[p] += radius; break;                                    // about the radius away
+        case 2: py[p] += (int64_t)(rng() % 4000000) - 2000000; px[p] -= 3 * radius; break;
+        default: py[p] += (int64_t)(rng() % (2 * radius + 1)) - radius;
+                 px[p] += (int64_t)(rng() % (2 * radius + 1)) - radius; break;
+      }
+    }
+    std::vector<int32_t> cand(P * k), fq(P * k), nc(P);
+    std::vector<int64_t> d2(P * k);
+    rtr::mm_edge_candidates(g, py.data(), px.data(), P, radius, k, cand.data(), d2.data(), fq.data(), nc.data());
+    for (size_t p = 0; p < P; ++p) {
+      std::vector<std::tuple<int64_t, int32_t, int32_t>> all;
+      for (size_t e = 0; e < E; ++e) {
+        if (!g.ok[e]) continue;
+        const rtr::MmEdge& ed = g.edges[e];
+        const int64_t by0 = ed.ay + std::min<int64_t>(ed.wy, 0), by1 = ed.ay + std::max<int64_t>(ed.wy, 0);
+        const int64_t bx0 = ed.ax + std::min<int64_t>(ed.wx, 0), bx1 = ed.ax + std::max<int64_t>(ed.wx, 0);
+        if (py[p] < by0 - radius || py[p] > by1 + radius || px[p] < bx0 - radius || px[p] > bx1 + radius) continue;
+        int64_t dd;
+        int32_t q;
+        rtr::mm_edge_project(ed, py[p], px[p], &dd, &q);
+        CHECK(q >= 0 && q <= rtr::kMmOne, "mm_edge_project: fq %d", q);
+        // against the true distance to the segment: fq rounds down by at most span / 2^16 along the
+        // edge, Q rounds by half a centimetre per axis
+        const long double wy = ed.wy, wx = ed.wx, ey = py[p] - ed.ay, ex = px[p] - ed.ax, l2 = wy * wy + wx * wx;
+        long double t = l2 > 0 ? (ey * wy + ex * wx) / l2 : 0;
+        t = std::min<long double>(1, std::max<long double>(0, t));
+        const long double truth = std::sqrt((ey - t * wy) * (ey - t * wy) + (ex - t * wx) * (ex - t * wx));
+        CHECK(std::fabs(std::sqrt((long double)dd) - truth) <= 1.0L + std::sqrt(l2) / 65536.0L,
+              "mm_edge_project: %lld cm2 against a true distance of %.3Lf cm", (long long)dd, truth);
+        if (dd <= radius * radius) all.emplace_back(dd, (int32_t)e, q);
+      }
+      std::sort(all.begin(), all.end());
+      const size_t want = std::min(all.size(), (size_t)k);
+      bool same = nc[p] == (int32_t)want;
+      for (size_t j = 0; same && j < (size_t)k; ++j)
+        same = j < want ? (d2[p * k + j] == std::get<0>(all[j]) && cand[p * k + j] == std::get<1>(all[j]) &&
+                           fq[p * k + j] == std::get<2>(all[j]))
+                        : (cand[p * k + j] == -1 && d2[p * k + j] == -1 && fq[p * k + j] == -1);
+      CHECK(same, "mm_edge_candidates differs from the scan (E=%zu k=%d radius=%lld fix %zu)", E, k, (long long)radius, p);
+    }
+  }
+}
+
 // map_match.h mm_viterbi: on random costs (infeasible routes, detours beyond the limit, equal
 // costs, costs at the parameter maxima) the result is a valid segmentation — choices inside
 // n_cand, segment indices rising by at most one, feasible transitions inside a segment, none
@@ -1052,6 +1138,7 @@ int main(int argc, char** argv) {
   fuzz_alternatives(rng, iters);
   fuzz_history(rng, iters);
   fuzz_mm_candidates(rng, iters);
+  fuzz_mm_edge_candidates(rng, iters);
   fuzz_mm_viterbi(rng, iters);
   fuzz_avoid_mask(rng, iters);
   fuzz_tw_improve(rng, iters);

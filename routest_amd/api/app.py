@@ -547,7 +547,8 @@ def create_app(services: Optional[Services] = None, settings: Optional[Settings]
     async def match(request: Request):
         """Map-match GPS traces to the road graph under the request's context (OSRM's match shape
         per trace; routing/mapmatch.py): ``matchings`` (one connected node path per segment) and
-        ``tracepoints`` (one per fix, null when unmatched)."""
+        ``tracepoints`` (one per fix, null when unmatched).  ``"snap": "edge"`` snaps the fixes to
+        points along road edges (routing/mapmatch_edge.py); the default ``"node"`` to graph nodes."""
         body = await _json_body(request, silent=False)
         if isinstance(body, Response):
             return body

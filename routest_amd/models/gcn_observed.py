@@ -204,16 +204,31 @@ class Observations:
 
 
 def trips_from_traces(provider, traces: Sequence[Any], observed_seconds: Sequence[float], ctx=None, params=None,
-                      device=None) -> Tuple[List[Tuple[List[int], float]], List[int]]:
+                      device=None, snap: str = "node") -> Tuple[List[Tuple[List[int], float]], List[int]]:
     """Observed trips from GPS traces: each trace (a list of ``(lat, lon)`` fixes) is map-matched on
     the provider's road graph (``GraphProvider.match``, routing/mapmatch.py) and becomes ``(node
     path, observed seconds)`` when it matched in exactly one connected path with no unmatched fix.
     Returns the trips and the indices of the traces dropped (unmatched fixes, a break, or a path of
-    fewer than two nodes, which carries nothing to learn from)."""
+    fewer than two nodes, which carries nothing to learn from).  ``snap="edge"`` matches to points
+    along edges (routing/mapmatch_edge.py); the node path then runs from the tail of the first
+    fix's edge over the nodes passed to the head of the last fix's edge."""
     if len(traces) != len(observed_seconds):
         raise ValueError("one observed duration per trace")
+    if snap not in ("node", "edge"):
+        raise ValueError("snap: 'node' or 'edge'")
     trips: List[Tuple[List[int], float]] = []
     dropped: List[int] = []
+    if snap == "edge":
+        from ..routing.mapmatch_edge import node_path
+        for i, r in enumerate(provider.match(traces, ctx=ctx, params=params, device=device, snap="edge")
+                              if len(traces) else []):
+            path = (node_path(provider.g, r, 0)
+                    if r["n_segments"] == 1 and len(r["matchings"]) == 1 and bool((r["edge"] >= 0).all()) else [])
+            if len(path) >= 2:
+                trips.append(([int(v) for v in path], float(observed_seconds[i])))
+            else:
+                dropped.append(i)
+        return trips, dropped
     for i, r in enumerate(provider.match(traces, ctx=ctx, params=params, device=device) if len(traces) else []):
         whole = (r["n_segments"] == 1 and len(r["matchings"]) == 1 and bool((r["matched"] >= 0).all())
                  and len(r["matchings"][0]["nodes"]) >= 2)

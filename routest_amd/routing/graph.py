@@ -756,15 +756,23 @@ class GraphProvider(HaversineProvider):
                             "reach_m": float(em[mask[eu] & mask[ev]].sum())})
         return out
 
-    def match(self, traces: Sequence[Any], ctx=None, params=None, device=None) -> List[Dict[str, Any]]:
+    def match(self, traces: Sequence[Any], ctx=None, params=None, device=None,
+              snap: str = "node") -> List[Dict[str, Any]]:
         """Map-match GPS traces (each a list of ``(lat, lon)`` fixes) to connected node paths under
         the request's context: ``routing.mapmatch.match_traces`` on the CCH router of ``device``
-        (HIP kernels on a GPU, the host reference otherwise)."""
+        (HIP kernels on a GPU, the host reference otherwise).  ``snap="edge"`` snaps the fixes to
+        points along road edges instead of graph nodes (``routing.mapmatch_edge.match_traces_edge``,
+        whose result dicts differ: ``edge`` / ``fq`` / ``proj`` in place of ``matched``)."""
+        if snap not in ("node", "edge"):
+            raise ValueError("snap: 'node' or 'edge'")
         if self.engine == "astar":
             raise ProviderError("map matching needs the CCH router: ROUTEST_ROUTER=astar has no batched pair "
                                 "metres under a context (unset it or use ROUTEST_ROUTER=cch)")
         from .mapmatch import match_traces
+        from .mapmatch_edge import match_traces_edge
         with self.pinned_metric(ctx, device) as key:
+            if snap == "edge":
+                return match_traces_edge(self.router(device), self.g, traces, key, params)
             return match_traces(self.router(device), self.g, traces, key, params)
 
     def directions(self, coords: List[List[float]], profile: str, ctx=None) -> Dict[str, Any]:

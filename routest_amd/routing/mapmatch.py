@@ -628,11 +628,21 @@ def parse_match_request(data: Any) -> Tuple[List[np.ndarray], MatchParams]:
 
 def match_response(provider, data: Any, ctx=None, device=None) -> Dict[str, Any]:
     """The endpoint's answer for a road-graph provider: OSRM-shaped ``matchings`` / ``tracepoints``
-    per trace."""
+    per trace.  ``"snap": "edge"`` answers the edge-based matcher's shape
+    (:func:`mapmatch_edge.edge_match_response`); absent or ``"node"`` it is this module's."""
     from .avoid import check_provider
     traces, params = parse_match_request(data)
+    snap = data.get("snap", "node")
+    if snap not in ("node", "edge") or not isinstance(snap, str):
+        raise ValueError("snap: 'node' or 'edge'")
     g = provider.g
     check_provider(provider, ctx)
+    if snap == "edge":
+        from .mapmatch_edge import edge_match_response
+        ans = {"code": "Ok", "traces": edge_match_response(provider, traces, params, ctx=ctx, device=device)}
+        if getattr(ctx, "avoid", None) is not None:
+            ans["avoid"] = ctx.avoid.summary()
+        return ans
     res = provider.match(traces, ctx=ctx, params=params, device=device)
 
     def lonlat(n: int) -> List[float]:
