@@ -444,19 +444,41 @@ torch::Tensor route_haversine_matrix(torch::Tensor lat, torch::Tensor lon, torch
   return D;
 }
 
+// The checks the route bindings (K6, K6b-K6e) share; the message texts are part of the interface.
+static void check_route_D(const torch::Tensor& D, const torch::Tensor* T = nullptr) {
+  TORCH_CHECK(D.scalar_type() == torch::kFloat64 && D.dim() == 3 && D.size(1) == D.size(2),
+              "D must be f64 [R,NM,NM]");
+  if (T)
+    TORCH_CHECK(T->scalar_type() == torch::kFloat64 && T->sizes() == D.sizes(), "T must be f64 [R,NM,NM]");
+}
+static const char* route_dtype_name(torch::ScalarType ty) {
+  TORCH_CHECK(ty == torch::kFloat64 || ty == torch::kInt64 || ty == torch::kInt32 || ty == torch::kUInt8,
+              "route checks know f64, i64, i32 and u8");
+  return ty == torch::kFloat64 ? "f64" : ty == torch::kInt64 ? "i64" : ty == torch::kInt32 ? "i32" : "u8";
+}
+// t is a [R] vector of dtype ty
+static void check_route_vec(const torch::Tensor& t, torch::ScalarType ty, int R, const char* what) {
+  TORCH_CHECK(t.scalar_type() == ty && t.numel() == R, what, " must be ", route_dtype_name(ty), " [R]");
+}
+// every tensor of ts is a [R, NM] array of dtype ty
+static void check_route_rows(std::initializer_list<const torch::Tensor*> ts, torch::ScalarType ty, int R, int NM,
+                             const char* what, const char* unit = "") {
+  for (const torch::Tensor* t : ts)
+    TORCH_CHECK(t->scalar_type() == ty && t->numel() == (int64_t)R * NM, what, " must be ",
+                route_dtype_name(ty), " [R,NM]", unit);
+}
+
 std::vector<torch::Tensor> route_greedy_cvrp(torch::Tensor D, torch::Tensor npts,
                                              torch::Tensor demand, torch::Tensor cap,
                                              torch::Tensor maxd) {
   for (auto* t : {&D, &npts, &demand, &cap, &maxd}) check_dev(*t, "route tensor");
-  TORCH_CHECK(D.scalar_type() == torch::kFloat64 && D.dim() == 3 && D.size(1) == D.size(2),
-              "D must be f64 [R,NM,NM]");
+  check_route_D(D);
   const int R = (int)D.size(0), NM = (int)D.size(1);
   TORCH_CHECK(NM <= 4096, "at most 4095 stops per request");
-  TORCH_CHECK(npts.scalar_type() == torch::kInt32 && npts.numel() == R, "npts must be i32 [R]");
-  TORCH_CHECK(demand.scalar_type() == torch::kFloat64 && demand.numel() == (int64_t)R * NM,
-              "demand must be f64 [R,NM]");
-  TORCH_CHECK(cap.scalar_type() == torch::kFloat64 && cap.numel() == R, "cap must be f64 [R]");
-  TORCH_CHECK(maxd.scalar_type() == torch::kFloat64 && maxd.numel() == R, "maxd must be f64 [R]");
+  check_route_vec(npts, torch::kInt32, R, "npts");
+  check_route_rows({&demand}, torch::kFloat64, R, NM, "demand");
+  check_route_vec(cap, torch::kFloat64, R, "cap");
+  check_route_vec(maxd, torch::kFloat64, R, "maxd");
   const c10::DeviceGuard guard(D.device());
   auto iopt = D.options().dtype(torch::kInt32);
   auto visit = torch::empty({R, NM}, iopt);
@@ -477,18 +499,15 @@ std::vector<torch::Tensor> route_improve_trips(torch::Tensor D, torch::Tensor np
                                                torch::Tensor visit, torch::Tensor trip_of,
                                                torch::Tensor status, torch::Tensor flag) {
   for (auto* t : {&D, &npts, &maxd, &visit, &trip_of, &status, &flag}) check_dev(*t, "route tensor");
-  TORCH_CHECK(D.scalar_type() == torch::kFloat64 && D.dim() == 3 && D.size(1) == D.size(2),
-              "D must be f64 [R,NM,NM]");
+  check_route_D(D);
   const int R = (int)D.size(0), NM = (int)D.size(1);
   TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
-  TORCH_CHECK(npts.scalar_type() == torch::kInt32 && npts.numel() == R, "npts must be i32 [R]");
-  TORCH_CHECK(maxd.scalar_type() == torch::kFloat64 && maxd.numel() == R, "maxd must be f64 [R]");
-  TORCH_CHECK(visit.scalar_type() == torch::kInt32 && visit.numel() == (int64_t)R * NM,
-              "visit must be i32 [R,NM]");
-  TORCH_CHECK(trip_of.scalar_type() == torch::kInt32 && trip_of.numel() == (int64_t)R * NM,
-              "trip_of must be i32 [R,NM]");
-  TORCH_CHECK(status.scalar_type() == torch::kInt32 && status.numel() == R, "status must be i32 [R]");
-  TORCH_CHECK(flag.scalar_type() == torch::kUInt8 && flag.numel() == R, "flag must be u8 [R]");
+  check_route_vec(npts, torch::kInt32, R, "npts");
+  check_route_vec(maxd, torch::kFloat64, R, "maxd");
+  check_route_rows({&visit}, torch::kInt32, R, NM, "visit");
+  check_route_rows({&trip_of}, torch::kInt32, R, NM, "trip_of");
+  check_route_vec(status, torch::kInt32, R, "status");
+  check_route_vec(flag, torch::kUInt8, R, "flag");
   const c10::DeviceGuard guard(D.device());
   auto iopt = D.options().dtype(torch::kInt32);
   auto lopt = D.options().dtype(torch::kInt64);
@@ -513,22 +532,18 @@ std::vector<torch::Tensor> route_exchange_trips(torch::Tensor D, torch::Tensor n
                                                 torch::Tensor flag, int64_t move_cap) {
   for (auto* t : {&D, &npts, &demand, &cap, &maxd, &visit, &trip_of, &ntrips, &status, &flag})
     check_dev(*t, "route tensor");
-  TORCH_CHECK(D.scalar_type() == torch::kFloat64 && D.dim() == 3 && D.size(1) == D.size(2),
-              "D must be f64 [R,NM,NM]");
+  check_route_D(D);
   const int R = (int)D.size(0), NM = (int)D.size(1);
   TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
-  TORCH_CHECK(npts.scalar_type() == torch::kInt32 && npts.numel() == R, "npts must be i32 [R]");
-  TORCH_CHECK(demand.scalar_type() == torch::kFloat64 && demand.numel() == (int64_t)R * NM,
-              "demand must be f64 [R,NM]");
-  TORCH_CHECK(cap.scalar_type() == torch::kFloat64 && cap.numel() == R, "cap must be f64 [R]");
-  TORCH_CHECK(maxd.scalar_type() == torch::kFloat64 && maxd.numel() == R, "maxd must be f64 [R]");
-  TORCH_CHECK(visit.scalar_type() == torch::kInt32 && visit.numel() == (int64_t)R * NM,
-              "visit must be i32 [R,NM]");
-  TORCH_CHECK(trip_of.scalar_type() == torch::kInt32 && trip_of.numel() == (int64_t)R * NM,
-              "trip_of must be i32 [R,NM]");
-  TORCH_CHECK(ntrips.scalar_type() == torch::kInt32 && ntrips.numel() == R, "ntrips must be i32 [R]");
-  TORCH_CHECK(status.scalar_type() == torch::kInt32 && status.numel() == R, "status must be i32 [R]");
-  TORCH_CHECK(flag.scalar_type() == torch::kUInt8 && flag.numel() == R, "flag must be u8 [R]");
+  check_route_vec(npts, torch::kInt32, R, "npts");
+  check_route_rows({&demand}, torch::kFloat64, R, NM, "demand");
+  check_route_vec(cap, torch::kFloat64, R, "cap");
+  check_route_vec(maxd, torch::kFloat64, R, "maxd");
+  check_route_rows({&visit}, torch::kInt32, R, NM, "visit");
+  check_route_rows({&trip_of}, torch::kInt32, R, NM, "trip_of");
+  check_route_vec(ntrips, torch::kInt32, R, "ntrips");
+  check_route_vec(status, torch::kInt32, R, "status");
+  check_route_vec(flag, torch::kUInt8, R, "flag");
   TORCH_CHECK(move_cap >= -1 && move_cap <= INT_MAX, "move_cap must be -1 (default) or a move count");
   const c10::DeviceGuard guard(D.device());
   auto iopt = D.options().dtype(torch::kInt32);
@@ -558,20 +573,15 @@ std::vector<torch::Tensor> route_tw_trips(torch::Tensor D, torch::Tensor T, torc
                                           torch::Tensor flag) {
   for (auto* t : {&D, &T, &npts, &demand, &cap, &maxd, &open, &close, &service, &flag})
     check_dev(*t, "route tensor");
-  TORCH_CHECK(D.scalar_type() == torch::kFloat64 && D.dim() == 3 && D.size(1) == D.size(2),
-              "D must be f64 [R,NM,NM]");
-  TORCH_CHECK(T.scalar_type() == torch::kFloat64 && T.sizes() == D.sizes(), "T must be f64 [R,NM,NM]");
+  check_route_D(D, &T);
   const int R = (int)D.size(0), NM = (int)D.size(1);
   TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
-  TORCH_CHECK(npts.scalar_type() == torch::kInt32 && npts.numel() == R, "npts must be i32 [R]");
-  TORCH_CHECK(demand.scalar_type() == torch::kFloat64 && demand.numel() == (int64_t)R * NM,
-              "demand must be f64 [R,NM]");
-  TORCH_CHECK(cap.scalar_type() == torch::kFloat64 && cap.numel() == R, "cap must be f64 [R]");
-  TORCH_CHECK(maxd.scalar_type() == torch::kFloat64 && maxd.numel() == R, "maxd must be f64 [R]");
-  for (auto* t : {&open, &close, &service})
-    TORCH_CHECK(t->scalar_type() == torch::kInt64 && t->numel() == (int64_t)R * NM,
-                "open, close and service must be i64 [R,NM] (milliseconds)");
-  TORCH_CHECK(flag.scalar_type() == torch::kUInt8 && flag.numel() == R, "flag must be u8 [R]");
+  check_route_vec(npts, torch::kInt32, R, "npts");
+  check_route_rows({&demand}, torch::kFloat64, R, NM, "demand");
+  check_route_vec(cap, torch::kFloat64, R, "cap");
+  check_route_vec(maxd, torch::kFloat64, R, "maxd");
+  check_route_rows({&open, &close, &service}, torch::kInt64, R, NM, "open, close and service", " (milliseconds)");
+  check_route_vec(flag, torch::kUInt8, R, "flag");
   const c10::DeviceGuard guard(D.device());
   auto iopt = D.options().dtype(torch::kInt32);
   auto lopt = D.options().dtype(torch::kInt64);
@@ -603,25 +613,19 @@ torch::Tensor route_tw_improve(torch::Tensor D, torch::Tensor T, torch::Tensor n
   for (auto* t : {&D, &T, &npts, &demand, &cap, &maxd, &open, &close, &service, &visit, &trip_of, &ntrips, &status,
                   &arrival, &start, &flag})
     check_dev(*t, "route tensor");
-  TORCH_CHECK(D.scalar_type() == torch::kFloat64 && D.dim() == 3 && D.size(1) == D.size(2),
-              "D must be f64 [R,NM,NM]");
-  TORCH_CHECK(T.scalar_type() == torch::kFloat64 && T.sizes() == D.sizes(), "T must be f64 [R,NM,NM]");
+  check_route_D(D, &T);
   const int R = (int)D.size(0), NM = (int)D.size(1);
   TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
-  TORCH_CHECK(npts.scalar_type() == torch::kInt32 && npts.numel() == R, "npts must be i32 [R]");
-  TORCH_CHECK(demand.scalar_type() == torch::kFloat64 && demand.numel() == (int64_t)R * NM,
-              "demand must be f64 [R,NM]");
-  TORCH_CHECK(cap.scalar_type() == torch::kFloat64 && cap.numel() == R, "cap must be f64 [R]");
-  TORCH_CHECK(maxd.scalar_type() == torch::kFloat64 && maxd.numel() == R, "maxd must be f64 [R]");
-  for (auto* t : {&open, &close, &service, &arrival, &start})
-    TORCH_CHECK(t->scalar_type() == torch::kInt64 && t->numel() == (int64_t)R * NM,
-                "open, close, service, arrival and start must be i64 [R,NM] (milliseconds)");
-  for (auto* t : {&visit, &trip_of})
-    TORCH_CHECK(t->scalar_type() == torch::kInt32 && t->numel() == (int64_t)R * NM,
-                "visit and trip_of must be i32 [R,NM]");
-  TORCH_CHECK(ntrips.scalar_type() == torch::kInt32 && ntrips.numel() == R, "ntrips must be i32 [R]");
-  TORCH_CHECK(status.scalar_type() == torch::kInt32 && status.numel() == R, "status must be i32 [R]");
-  TORCH_CHECK(flag.scalar_type() == torch::kUInt8 && flag.numel() == R, "flag must be u8 [R]");
+  check_route_vec(npts, torch::kInt32, R, "npts");
+  check_route_rows({&demand}, torch::kFloat64, R, NM, "demand");
+  check_route_vec(cap, torch::kFloat64, R, "cap");
+  check_route_vec(maxd, torch::kFloat64, R, "maxd");
+  check_route_rows({&open, &close, &service, &arrival, &start}, torch::kInt64, R, NM,
+                   "open, close, service, arrival and start", " (milliseconds)");
+  check_route_rows({&visit, &trip_of}, torch::kInt32, R, NM, "visit and trip_of");
+  check_route_vec(ntrips, torch::kInt32, R, "ntrips");
+  check_route_vec(status, torch::kInt32, R, "status");
+  check_route_vec(flag, torch::kUInt8, R, "flag");
   const c10::DeviceGuard guard(D.device());
   auto stats = torch::zeros({R, 7}, D.options().dtype(torch::kInt64));
   RT_CHECK_HIP(rt::launch_tw_improve(

@@ -5,15 +5,8 @@
 // routest_amd/routing/improve.py; the host C++ is rtr::improve_trips (runtime/route_core.h).  All
 // three are compared with ==: every gain is an int64 sum, so the schedule below cannot change it.
 //
-// One TEAM of threads per request row, the row's trips one after the other:
-//   * small tier: rows with at most 32 stops, TEAM = one wavefront, four rows per 256-thread block
-//     (like K6); only wave barriers, so a wave may leave early;
-//   * large tier: rows with more stops, TEAM = one 1024-thread block (the sub-matrix of a long
-//     trip fills most of a CU's LDS, so the block's 16 waves are what hides the LDS latency);
-//     every branch around a __syncthreads depends only on values all threads read from LDS or from
-//     the same address.
-// Both tiers are launched over all rows and each row is handled by the tier its stop count picks;
-// the small tier also zeroes the statistics of rows that do not ask.
+// One TEAM of threads per request row (teams, tiers and the barrier discipline: route_team.h), the
+// row's trips one after the other; each tier also zeroes the statistics of its rows that do not ask.
 //
 // Per trip of k stops (2 <= k <= 128): the (k+1)^2 sub-matrix is gathered ONCE into LDS, quantized,
 // indexed by trip-local stop number (0 = depot, a = a-th stop of the greedy); the order lives in
@@ -30,77 +23,58 @@
 //      and keeps (max gain, then min (type, i, j));
 //   4. the team reduces (max gain, then min (type, i, j)); everyone applies the move to the LDS
 //      order, one element per thread.
-// The per-lane loops of step 3 hold no barrier and no cross-lane operation; every loop that does
-// is bounded by values the whole team holds.  No global atomics, nothing waits on another team.
-#include <climits>
-
-#include "common.h"
 #include "ops.h"
+#include "route_team.h"
 
 namespace rt {
 
 namespace {
 
-constexpr long long kBig = 1LL << 50;
+using namespace team;
+
 constexpr long long kNever = -(1LL << 62);  // a row term that keeps a gain below 0 whatever is added
-constexpr int kMaxStops = 128;
-constexpr int kSmallStops = 32;
-constexpr int kLargeTeam = 1024;
 
-__device__ __forceinline__ long long quantize_mm(double x) {
-  if (!(x >= 0.0) || x >= 1099511627776.0) return kBig;  // NaN, +-inf, negatives, >= 2^40
-  return __double2ll_rn(x * 1000.0);
-}
-
-// LDS of one team, carved from the dynamic region (every offset a multiple of 16).
-__host__ __device__ constexpr int improve_stride(int kc) { return (kc + 1) | 1; }
-__host__ __device__ constexpr size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-__host__ __device__ constexpr size_t improve_team_bytes(int kc) {
-  return align16((size_t)(kc + 1) * improve_stride(kc) * 8)  // Q
-         + 9 * align16((size_t)(kc + 2) * 8)                 // f, b, pf, pb, row[4], dv
-         + 3 * align16((size_t)(kc + 2) * 4)                 // node, ord, win
-         + 128 + 64 + 16;                                    // red_g[16] | red_c[16] | misc[4]
-}
-
-template <int TEAM>
-__device__ __forceinline__ void team_sync() {
-  if constexpr (TEAM == 64) {
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS traffic is done
-    __builtin_amdgcn_wave_barrier();
-  } else {
-    __syncthreads();
+// LDS of one team (offsets in bytes), for a stop capacity of kc
+struct ImproveLds {
+  size_t Q = 0, f = 0, b = 0, pf = 0, pb = 0, row = 0, dv = 0, node = 0, ord = 0, win = 0, redg = 0, redc = 0,
+         misc = 0, bytes = 0;
+  __host__ __device__ constexpr explicit ImproveLds(int kc) {
+    LdsCarve c;
+    Q = c.take(8, (size_t)(kc + 1) * matrix_stride(kc));
+    f = c.take(8, kc + 2);
+    b = c.take(8, kc + 2);
+    pf = c.take(8, kc + 2);
+    pb = c.take(8, kc + 2);
+    row = c.take(8, kc + 2, 4);  // [kc + 2][4]: c0, rem[1], rem[2], rem[3]
+    dv = c.take(8, kc + 2);
+    node = c.take(4, kc + 2);
+    ord = c.take(4, kc + 2);
+    win = c.take(4, kc + 2);     // t[i-1] | t[i] << 8 | t[i+1] << 16 | t[i+2] << 24
+    redg = c.take(8, 16);
+    redc = c.take(4, 16);
+    misc = c.take(4, 4);         // [0] end of the trip, [1] bad stop number, [2] keep
+    bytes = c.bytes;
   }
-}
-
-__device__ __forceinline__ long long wave_first(long long v) {
-  const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffLL));
-  const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
-  return ((long long)hi << 32) | (unsigned int)lo;
-}
+};
+static_assert(ImproveLds(32).bytes == 11808 && ImproveLds(128).bytes == 144288, "the layout is fixed");
 
 // a move as one int that orders like (type, i, j): i, j <= 128
 __device__ __forceinline__ int move_code(int type, int i, int j) { return (type << 16) | (i << 8) | j; }
 
-// KC: stop capacity of the LDS carve (the launch sizes the dynamic region for it).
+// KC: stop capacity of the LDS carve (the launch sizes the dynamic region for it).  It must stay the
+// first parameter: launch_two_tiers passes it there, in front of the launch's own arguments.
 template <int TEAM>
-__global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void improve_trips_kernel(
-    const double* __restrict__ D, const int* __restrict__ npts, const double* __restrict__ maxd,
-    const unsigned char* __restrict__ flag, const int* __restrict__ status, int R, int NM, int KC,
+__global__ __launch_bounds__(Team<TEAM>::BLOCK) void improve_trips_kernel(
+    int KC, const double* __restrict__ D, const int* __restrict__ npts, const double* __restrict__ maxd,
+    const unsigned char* __restrict__ flag, const int* __restrict__ status, int R, int NM,
     int* __restrict__ visit, const int* __restrict__ trip_of, int* __restrict__ moves_out,
     int* __restrict__ changed_out, long long* __restrict__ before_out,
     long long* __restrict__ after_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int TEAMS = TEAM == 64 ? 4 : 1;
-  constexpr int WAVES = TEAM / 64;
-  const int team = TEAM == 64 ? (int)(threadIdx.x >> 6) : 0;
-  const int tid = TEAM == 64 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
-  const int r = blockIdx.x * TEAMS + team;
-  if (r >= R) return;  // small tier: wave-uniform, no block barrier below; large tier: never taken
-  int n = npts[r];
-  n = n < 0 ? 0 : (n > NM ? NM : n);
-  const int ns = n > 0 ? n - 1 : 0;
-  const bool small_row = ns <= kSmallStops;
-  if (small_row != (TEAM == 64)) return;  // the other tier's row (uniform over the team)
+  using Tm = Team<TEAM>;
+  const Row rw = Tm::row(npts, R, NM);
+  if (!rw.mine) return;
+  const int tid = rw.tid, r = rw.r, n = rw.n, ns = rw.ns;
   const bool asks = flag[r] != 0 && status[r] == 0;
   if (!asks || ns == 0) {
     if (tid == 0) {
@@ -112,25 +86,22 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void improve_trips_kernel(
     return;
   }
 
-  unsigned char* base = smem + (size_t)team * improve_team_bytes(KC);
-  const int S = improve_stride(KC);
-  const size_t vec8 = align16((size_t)(KC + 2) * 8), vec4 = align16((size_t)(KC + 2) * 4);
-  long long* sQ = (long long*)base;
-  base += align16((size_t)(KC + 1) * S * 8);
-  long long* s_f = (long long*)base;
-  long long* s_b = (long long*)(base + vec8);
-  long long* s_pf = (long long*)(base + 2 * vec8);
-  long long* s_pb = (long long*)(base + 3 * vec8);
-  long long* s_row = (long long*)(base + 4 * vec8);  // [KC + 2][4]: c0, rem[1], rem[2], rem[3]
-  double* s_dv = (double*)(base + 8 * vec8);
-  base += 9 * vec8;
-  int* s_node = (int*)base;
-  int* s_ord = (int*)(base + vec4);
-  unsigned* s_win = (unsigned*)(base + 2 * vec4);    // t[i-1] | t[i] << 8 | t[i+1] << 16 | t[i+2] << 24
-  base += 3 * vec4;
-  long long* s_redg = (long long*)base;
-  int* s_redc = (int*)(base + 128);
-  int* s_misc = (int*)(base + 192);  // [0] end of the trip, [1] bad stop number, [2] keep
+  const ImproveLds L(KC);
+  unsigned char* base = smem + (size_t)rw.team * L.bytes;
+  const int S = matrix_stride(KC);
+  long long* sQ = (long long*)(base + L.Q);
+  long long* s_f = (long long*)(base + L.f);
+  long long* s_b = (long long*)(base + L.b);
+  long long* s_pf = (long long*)(base + L.pf);
+  long long* s_pb = (long long*)(base + L.pb);
+  long long* s_row = (long long*)(base + L.row);
+  double* s_dv = (double*)(base + L.dv);
+  int* s_node = (int*)(base + L.node);
+  int* s_ord = (int*)(base + L.ord);
+  unsigned* s_win = (unsigned*)(base + L.win);
+  long long* s_redg = (long long*)(base + L.redg);
+  int* s_redc = (int*)(base + L.redc);
+  int* s_misc = (int*)(base + L.misc);
 
   const double* d = D + (size_t)r * NM * NM;
   int* vrow = visit + (size_t)r * NM;
@@ -140,21 +111,19 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void improve_trips_kernel(
   int tot_moves = 0, tot_changed = 0;
   long long tot_before = 0, tot_after = 0;
 
+  if (tid == 0) s_misc[1] = 0;  // only a bad trip sets it, and that ends the row: cleared once
   int pos = 0;
   while (pos < ns) {
     // ---- the trip's extent: the first position whose successor belongs to another trip
     const int tr = trow[pos];
-    if (tid == 0) {
-      s_misc[0] = ns;
-      s_misc[1] = 0;
-    }
-    team_sync<TEAM>();
+    if (tid == 0) s_misc[0] = ns;
+    Tm::sync();
     for (int p = pos + tid; p < ns; p += TEAM)
       if (trow[p] == tr && (p + 1 == ns || trow[p + 1] != tr)) atomicMin(&s_misc[0], p + 1);
-    team_sync<TEAM>();
+    Tm::sync();
     const int end = s_misc[0];
     const int k = end - pos;  // >= 1
-    team_sync<TEAM>();
+    Tm::sync();
 
     // ---- the greedy's length of the trip, from global memory (any k)
     long long part = 0;
@@ -168,22 +137,15 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void improve_trips_kernel(
         part += quantize_mm(d[(size_t)a * NM + b]);
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-    long long before = part;
-    if constexpr (TEAM != 64) {
-      if ((tid & 63) == 0) s_redg[tid >> 6] = part;
-      if (bad) s_misc[1] = 1;
-      __syncthreads();
-      before = 0;
-#pragma unroll
-      for (int w = 0; w < WAVES; ++w) before += s_redg[w];
-      bad = s_misc[1] != 0;
-      __syncthreads();
-    } else {
+    // the large tier's flag rides on the sum's barriers: set before its first, read behind its last.
+    // Nothing clears it again, and the next trip can set it only behind that trip's three barriers.
+    if constexpr (TEAM == 64) {
       bad = __ballot(bad) != 0ULL;
+    } else if (bad) {
+      s_misc[1] = 1;
     }
-    before = wave_first(before);
+    const long long before = Tm::sum(part, s_redg, tid);
+    if constexpr (TEAM != 64) bad = s_misc[1] != 0;
     if (bad) break;  // a stop number outside the row: not K6's output, leave the rest alone
     tot_before += before;
     if (k < 2 || k > kMaxStops || k > KC) {
@@ -198,20 +160,18 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void improve_trips_kernel(
       s_ord[a] = a;
     }
     if (tid == 0) s_ord[k + 1] = 0;
-    team_sync<TEAM>();
+    Tm::sync();
     const int k1 = k + 1;
     for (int c = tid; c < k1 * k1; c += TEAM) {
       const int a = c / k1, b = c - a * k1;
       sQ[a * S + b] = quantize_mm(d[(size_t)s_node[a] * NM + s_node[b]]);
     }
-    team_sync<TEAM>();
+    Tm::sync();
 
     // ---- best-improvement search
-    // a lane's insertion point / reversal end j and its first row; JW lanes per row
-    const int jsh = 32 - __builtin_clz(k);  // JW = 2^jsh >= k + 1 (k >= 2); <= TEAM in both tiers
-    const int j = tid & ((1 << jsh) - 1);
-    const int i0 = 1 + (tid >> jsh);
-    const int istep = TEAM >> jsh;
+    // a lane's insertion point / reversal end j and its first row; 2^sh >= k + 1 lanes per row
+    const Lanes ln = Tm::split(k + 1, tid);
+    const int j = ln.col0, i0 = 1 + ln.row0, istep = ln.rstep;
     int moves = 0;
     long long after = before;
     for (;;) {
@@ -220,7 +180,7 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void improve_trips_kernel(
         s_f[p] = sQ[a * S + b];
         s_b[p] = sQ[b * S + a];
       }
-      team_sync<TEAM>();
+      Tm::sync();
       // prefix sums over positions: pf[p] = sum_{x < p} f[x]; the segment part of the Or-opt gains
       for (int p = tid; p <= k + 1; p += TEAM) {
         long long f = 0, b = 0;
@@ -244,7 +204,7 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void improve_trips_kernel(
         s_row[i * 4 + 2] = i + 1 <= k ? fp + s_f[i + 1] - qp[t2] : kNever;
         s_row[i * 4 + 3] = i + 2 <= k ? fp + s_f[i + 2] - qp[t3] : kNever;
       }
-      team_sync<TEAM>();
+      Tm::sync();
       after = s_pf[k + 1];
       if (moves >= 4 * k) break;
 
@@ -276,36 +236,8 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void improve_trips_kernel(
           if (front || j > i + 2) take(row[3] + ins - sQ[t2 * S + tj1], move_code(3, i, j));
         }
       }
-      // (max gain, then min move code) over the wave, then over the team
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const long long og = __shfl_xor(bg, o);
-        const int oc = __shfl_xor(bc, o);
-        if (og > bg || (og == bg && oc < bc)) {
-          bg = og;
-          bc = oc;
-        }
-      }
-      if constexpr (TEAM != 64) {
-        if ((tid & 63) == 0) {
-          s_redg[tid >> 6] = bg;
-          s_redc[tid >> 6] = bc;
-        }
-        __syncthreads();
-        bg = s_redg[0];
-        bc = s_redc[0];
-#pragma unroll
-        for (int w = 1; w < WAVES; ++w) {
-          const long long og = s_redg[w];
-          const int oc = s_redc[w];
-          if (og > bg || (og == bg && oc < bc)) {
-            bg = og;
-            bc = oc;
-          }
-        }
-      }
-      bg = wave_first(bg);
-      bc = __builtin_amdgcn_readfirstlane(bc);
+      // (max gain, then min move code) over the team
+      Tm::best(bg, bc, s_redg, s_redc, tid);
       if (bg <= 0) break;
 
       // ---- apply: every thread moves at most one element of the order
@@ -332,9 +264,9 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void improve_trips_kernel(
       const int p = lo + tid;
       int val = 0;
       if (p <= hi) val = s_ord[src];
-      team_sync<TEAM>();
+      Tm::sync();
       if (p <= hi) s_ord[p] = val;
-      team_sync<TEAM>();
+      Tm::sync();
       ++moves;
     }
 
@@ -343,13 +275,13 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void improve_trips_kernel(
     if (moves > 0) {
       for (int p = tid; p <= k; p += TEAM)
         s_dv[p] = d[(size_t)s_node[s_ord[p]] * NM + s_node[s_ord[p + 1]]];
-      team_sync<TEAM>();
+      Tm::sync();
       if (tid == 0) {
         double s = 0.0;
         for (int p = 0; p < k; ++p) s += s_dv[p];
         s_misc[2] = (s + s_dv[k]) <= MD ? 1 : 0;
       }
-      team_sync<TEAM>();
+      Tm::sync();
       keep = s_misc[2] != 0;
     }
     if (keep) {
@@ -360,7 +292,7 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void improve_trips_kernel(
     } else {
       tot_after += before;
     }
-    team_sync<TEAM>();
+    Tm::sync();
     pos = end;
   }
   if (tid == 0) {
@@ -378,31 +310,10 @@ hipError_t launch_improve_trips(const double* D, const int* npts, const double* 
                                 int* visit, const int* trip_of, int* moves, int* trips_changed,
                                 long long* len_before_q, long long* len_after_q,
                                 hipStream_t stream) {
-  if (R == 0) return hipSuccess;
-  if (NM < 1 || NM > 4096) return hipErrorInvalidValue;
-  // small tier: rows of at most 32 stops, a wavefront each
-  {
-    const int kc = NM - 1 < kSmallStops ? (NM - 1 < 1 ? 1 : NM - 1) : kSmallStops;
-    const size_t lds = 4 * improve_team_bytes(kc);
-    hipLaunchKernelGGL(improve_trips_kernel<64>, dim3((R + 3) / 4), dim3(256), lds, stream, D, npts,
-                       maxd, flag, status, R, NM, kc, visit, trip_of, moves, trips_changed,
-                       len_before_q, len_after_q);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  if (NM - 1 <= kSmallStops) return hipSuccess;
-  // large tier: a 1024-thread workgroup each; up to 143 KB of LDS (k = 128) needs the opt-in size
-  const int kc = NM - 1 < kMaxStops ? NM - 1 : kMaxStops;
-  const size_t lds = improve_team_bytes(kc);
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)improve_trips_kernel<kLargeTeam>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(improve_trips_kernel<kLargeTeam>, dim3(R), dim3(kLargeTeam), lds, stream, D,
-                     npts, maxd, flag, status, R, NM, kc, visit, trip_of, moves, trips_changed,
-                     len_before_q, len_after_q);
-  return hipGetLastError();
+  // up to 141 KB of LDS per large row (k = 128)
+  return team::launch_two_tiers<ImproveLds>(improve_trips_kernel<64>, improve_trips_kernel<team::kLargeTeam>,
+                                            R, NM, stream, D, npts, maxd, flag, status, R, NM, visit,
+                                            trip_of, moves, trips_changed, len_before_q, len_after_q);
 }
 
 }  // namespace rt

@@ -8,19 +8,12 @@
 // All three are compared with ==: every quantity the search orders by is an int64 sum, so the
 // schedule below cannot change it.
 //
-// One TEAM of threads per request row, with K6c / K6d's two tiers and their barrier discipline:
-//   * small tier: rows with at most 32 stops, TEAM = one wavefront, four rows per 256-thread block;
-//     only wave barriers, so a wave may leave early;
-//   * large tier: rows with 33..128 stops, TEAM = one 1024-thread block; every branch around a
-//     __syncthreads depends only on values all threads read from LDS (reduction results) or from the
-//     same global address.
-// Both tiers are launched over all rows and each row is handled by the tier its stop count picks.
+// One TEAM of threads per request row (teams, tiers and the barrier discipline: route_team.h).
 //
 // The row's two quantized matrices are gathered ONCE into LDS as int32 (an unusable entry is
 // INT_MAX, so the narrowing is exact), as K6d does, with open / close / service / demand (int64).
-// The order is K6c's flat array of stops grouped by trip in the trips' original order (a flat
-// position orders like (A, i)) with the trip of every position and every trip's start / count, in
-// two copies; an emptied trip keeps its index.  dep[] and z[] are kept per flat position.  Per move:
+// The order is route_team.h's flat order (a flat position orders like (A, i)); dep[] and z[] are
+// kept per flat position.  Per move:
 //   0. one lane per trip walks dep forwards and z backwards over its positions;
 //   1. per position p (stop s, trip A, index i, neighbours prev / next): nb = q(prev,s) + q(s,next),
 //      rem, whether A may lose s to another trip (bridge leg usable, Lq[A] - rem <= max_q, the next
@@ -38,185 +31,101 @@
 //      association matters); accepted: the copies change roles, Lq / Wq take the move's deltas;
 //      rejected: the first copy stays and the search ends.
 // At the end the non-empty trips are compacted: one lane per trip walks its schedule, the positions
-// go out one per thread and the waiting time by a team sum.  No global atomics, nothing waits on
-// another team; every loop that holds a barrier is bounded by values the whole team holds alike.
-#include <climits>
-
-#include "common.h"
+// go out one per thread and the waiting time by a team sum.
 #include "ops.h"
+#include "route_team.h"
 
 namespace rt {
 
 namespace {
 
-constexpr long long kBig = 1LL << 50;
-constexpr long long kUnbounded = 1LL << 62;
-constexpr int kUnusable = INT_MAX;
-constexpr int kMaxStops = 128;
-constexpr int kSmallStops = 32;
-constexpr int kLargeTeam = 1024;
+using namespace team;
 
-__device__ __forceinline__ long long quantize_mm(double x) {
-  if (!(x >= 0.0) || x >= 1099511627776.0) return kBig;  // NaN, +-inf, negatives, >= 2^40
-  return __double2ll_rn(x * 1000.0);
-}
-
-// a matrix entry as the int32 the LDS holds: INT_MAX for every value >= 2^31 - 1
-__device__ __forceinline__ int quantize_entry(double x) {
-  const long long v = quantize_mm(x);
-  return v >= (long long)kUnusable ? kUnusable : (int)v;
-}
-
-// cap_q / max_q: floor(x * 1000) below 2^40, unbounded from there; -1 for NaN and negatives
-__device__ __forceinline__ long long quantize_limit(double x) {
-  if (!(x >= 0.0)) return -1;
-  if (x >= 1099511627776.0) return kUnbounded;
-  return (long long)floor(x * 1000.0);
-}
-
-// LDS of one team, carved from the dynamic region (every offset a multiple of 16).
-__host__ __device__ constexpr int twi_stride(int kc) { return (kc + 1) | 1; }
-__host__ __device__ constexpr size_t ialign16(size_t b) { return (b + 15) & ~(size_t)15; }
-__host__ __device__ constexpr size_t twi_team_bytes(int kc) {
-  return 2 * ialign16((size_t)(kc + 1) * twi_stride(kc) * 4)  // Q, T
-         + 14 * ialign16((size_t)(kc + 4) * 8)  // open, close, sv, qd, dep, z, Lq, Wq, rem, nb, dv[2], dm[2]
-         + 12 * ialign16((size_t)(kc + 4) * 4)  // ord[2], tof[2], tst[2], cnt[2], pw, pn, rank, bnd
-         + 128 + 128 + 32;                      // red_g[16] | red_c[16] | misc[8]
-}
-
-template <int TEAM>
-__device__ __forceinline__ void team_sync() {
-  if constexpr (TEAM == 64) {
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS traffic is done
-    __builtin_amdgcn_wave_barrier();
-  } else {
-    __syncthreads();
+// LDS of one team (offsets in bytes), for a stop capacity of kc; [2]: two arrays of stride v8 / v4
+struct TwImproveLds {
+  size_t Q = 0, T = 0, open = 0, close = 0, sv = 0, qd = 0, dep = 0, z = 0, Lq = 0, Wq = 0, rem = 0, nb = 0,
+         dv = 0, dm = 0, ord = 0, tof = 0, tst = 0, cnt = 0, pw = 0, pn = 0, rank = 0, bnd = 0, redg = 0,
+         redc = 0, misc = 0, bytes = 0;
+  int v8 = 0, v4 = 0;
+  __host__ __device__ constexpr explicit TwImproveLds(int kc) {
+    LdsCarve c;
+    Q = c.take(4, (size_t)(kc + 1) * matrix_stride(kc));
+    T = c.take(4, (size_t)(kc + 1) * matrix_stride(kc));
+    open = c.take(8, kc + 4);
+    close = c.take(8, kc + 4);
+    sv = c.take(8, kc + 4);
+    qd = c.take(8, kc + 4);
+    dep = c.take(8, kc + 4);    // per flat position: the departure of its stop
+    z = c.take(8, kc + 4);      // per flat position: the latest start of its stop
+    Lq = c.take(8, kc + 4);     // per trip
+    Wq = c.take(8, kc + 4);
+    rem = c.take(8, kc + 4);    // per flat position
+    nb = c.take(8, kc + 4);
+    dv = c.take(8, kc + 4, 2);  // a touched trip's legs
+    dm = c.take(8, kc + 4, 2);  // ... and its stops' demands
+    ord = c.take(4, kc + 4, 2); // the order and its moved copy
+    tof = c.take(4, kc + 4, 2);
+    tst = c.take(4, kc + 4, 2);
+    cnt = c.take(4, kc + 4, 2);
+    pw = c.take(4, kc + 4);     // s | A << 8 | i << 16 | may-leave << 25 | may-shift << 26
+    pn = c.take(4, kc + 4);     // prev | next << 8
+    rank = c.take(4, kc + 4);
+    bnd = c.take(4, kc + 4);
+    redg = c.take(8, 16);
+    redc = c.take(8, 16);
+    misc = c.take(4, 8);        // [0], [1]: the two walks' verdicts
+    bytes = c.bytes;
+    v8 = (int)(align16((size_t)(kc + 4) * 8) / 8);
+    v4 = (int)(align16((size_t)(kc + 4) * 4) / 4);
   }
-}
+};
+static_assert(TwImproveLds(32).bytes == 14784 && TwImproveLds(128).bytes == 154560, "the layout is fixed");
 
-__device__ __forceinline__ long long wave_first(long long v) {
-  const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffLL));
-  const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
-  return ((long long)hi << 32) | (unsigned int)lo;
-}
-
-// the sum of v over the team, held by every thread (red: 16 words of the team's LDS)
+// KC: stop capacity of the LDS carve (the launch sizes the dynamic region for it).  It must stay the
+// first parameter: launch_two_tiers passes it there, in front of the launch's own arguments.
 template <int TEAM>
-__device__ __forceinline__ long long team_sum(long long v, long long* red, int tid) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if constexpr (TEAM != 64) {
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    v = 0;
-#pragma unroll
-    for (int w = 0; w < TEAM / 64; ++w) v += red[w];
-    __syncthreads();
-  }
-  return wave_first(v);
-}
-
-// (max g, then min c) over the team, held by every thread
-template <int TEAM>
-__device__ __forceinline__ void team_best(long long& g, long long& c, long long* red_g, long long* red_c,
-                                          int tid) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const long long og = __shfl_xor(g, o);
-    const long long oc = __shfl_xor(c, o);
-    if (og > g || (og == g && oc < c)) {
-      g = og;
-      c = oc;
-    }
-  }
-  if constexpr (TEAM != 64) {
-    if ((tid & 63) == 0) {
-      red_g[tid >> 6] = g;
-      red_c[tid >> 6] = c;
-    }
-    __syncthreads();
-    g = red_g[0];
-    c = red_c[0];
-#pragma unroll
-    for (int w = 1; w < TEAM / 64; ++w) {
-      const long long og = red_g[w];
-      const long long oc = red_c[w];
-      if (og > g || (og == g && oc < c)) {
-        g = og;
-        c = oc;
-      }
-    }
-    __syncthreads();
-  }
-  g = wave_first(g);
-  c = wave_first(c);
-}
-
-// a move as one word that orders like (type, A, i, B, j): A, B <= 127, i, j <= 128
-__device__ __forceinline__ long long move_code(int type, int A, int i, int B, int j) {
-  return ((long long)type << 32) | ((long long)A << 24) | ((long long)i << 16) | ((long long)B << 8) | j;
-}
-
-__device__ __forceinline__ long long max64(long long a, long long b) { return a > b ? a : b; }
-
-// KC: stop capacity of the LDS carve (the launch sizes the dynamic region for it).
-template <int TEAM>
-__global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void tw_improve_kernel(
-    const double* __restrict__ D, const double* __restrict__ T, const int* __restrict__ npts,
+__global__ __launch_bounds__(Team<TEAM>::BLOCK) void tw_improve_kernel(
+    int KC, const double* __restrict__ D, const double* __restrict__ T, const int* __restrict__ npts,
     const double* __restrict__ demand, const double* __restrict__ cap, const double* __restrict__ maxd,
     const long long* __restrict__ open, const long long* __restrict__ close,
-    const long long* __restrict__ service, const unsigned char* __restrict__ flag, int R, int NM, int KC,
+    const long long* __restrict__ service, const unsigned char* __restrict__ flag, int R, int NM,
     int* __restrict__ visit, int* __restrict__ trip_of, int* __restrict__ ntrips,
     const int* __restrict__ status, long long* __restrict__ arrival, long long* __restrict__ start,
     long long* __restrict__ stats) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int TEAMS = TEAM == 64 ? 4 : 1;
-  constexpr int TEAM_SHIFT = TEAM == 64 ? 6 : 10;
-  const int team = TEAM == 64 ? (int)(threadIdx.x >> 6) : 0;
-  const int tid = TEAM == 64 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
-  const int r = blockIdx.x * TEAMS + team;
-  if (r >= R) return;  // small tier: wave-uniform, no block barrier below; large tier: never taken
+  using Tm = Team<TEAM>;
+  const Row rw = Tm::row(npts, R, NM);
+  if (!rw.mine) return;
+  const int tid = rw.tid, r = rw.r, n = rw.n, ns = rw.ns;
   if (flag[r] == 0 || status[r] != 0) return;  // not asked for, or not planned: nothing is touched
-  int n = npts[r];
-  n = n < 0 ? 0 : (n > NM ? NM : n);
-  const int ns = n > 0 ? n - 1 : 0;
-  const bool small_row = ns <= kSmallStops;
-  if (small_row != (TEAM == 64)) return;  // the other tier's row (uniform over the team)
   if (ns == 0 || ns > kMaxStops || ns > KC) return;
 
-  unsigned char* base = smem + (size_t)team * twi_team_bytes(KC);
-  const int S = twi_stride(KC);
-  const size_t mat = ialign16((size_t)(KC + 1) * S * 4);
-  const size_t vec8 = ialign16((size_t)(KC + 4) * 8), vec4 = ialign16((size_t)(KC + 4) * 4);
-  int* sQ = (int*)base;
-  int* sT = (int*)(base + mat);
-  base += 2 * mat;
-  long long* s_open = (long long*)base;
-  long long* s_close = (long long*)(base + vec8);
-  long long* s_sv = (long long*)(base + 2 * vec8);
-  long long* s_qd = (long long*)(base + 3 * vec8);
-  long long* s_dep = (long long*)(base + 4 * vec8);  // per flat position: the departure of its stop
-  long long* s_z = (long long*)(base + 5 * vec8);    // per flat position: the latest start of its stop
-  long long* s_Lq = (long long*)(base + 6 * vec8);   // per trip
-  long long* s_Wq = (long long*)(base + 7 * vec8);
-  long long* s_rem = (long long*)(base + 8 * vec8);  // per flat position
-  long long* s_nb = (long long*)(base + 9 * vec8);
-  double* s_dv = (double*)(base + 10 * vec8);        // [2][KC + 4]: a touched trip's legs
-  double* s_dm = (double*)(base + 12 * vec8);        // [2][KC + 4]: ... and its stops' demands
-  base += 14 * vec8;
-  int* s_ord = (int*)base;                           // [2][KC + 4]: the order and its moved copy
-  int* s_tof = (int*)(base + 2 * vec4);              // [2][KC + 4]
-  int* s_tst = (int*)(base + 4 * vec4);              // [2][KC + 4]
-  int* s_cnt = (int*)(base + 6 * vec4);              // [2][KC + 4]
-  unsigned* s_pw = (unsigned*)(base + 8 * vec4);     // s | A << 8 | i << 16 | may-leave << 25 | may-shift << 26
-  unsigned* s_pn = (unsigned*)(base + 9 * vec4);     // prev | next << 8
-  int* s_rank = (int*)(base + 10 * vec4);
-  int* s_bnd = (int*)(base + 11 * vec4);
-  base += 12 * vec4;
-  long long* s_redg = (long long*)base;
-  long long* s_redc = (long long*)(base + 128);
-  int* s_misc = (int*)(base + 256);  // [0], [1]: the two walks' verdicts
-  const int V4 = (int)(vec4 / 4), V8 = (int)(vec8 / 8);
+  const TwImproveLds L(KC);
+  unsigned char* base = smem + (size_t)rw.team * L.bytes;
+  const int S = matrix_stride(KC), V4 = L.v4, V8 = L.v8;
+  int* sQ = (int*)(base + L.Q);
+  int* sT = (int*)(base + L.T);
+  long long* s_open = (long long*)(base + L.open);
+  long long* s_close = (long long*)(base + L.close);
+  long long* s_sv = (long long*)(base + L.sv);
+  long long* s_qd = (long long*)(base + L.qd);
+  long long* s_dep = (long long*)(base + L.dep);
+  long long* s_z = (long long*)(base + L.z);
+  long long* s_Lq = (long long*)(base + L.Lq);
+  long long* s_Wq = (long long*)(base + L.Wq);
+  long long* s_rem = (long long*)(base + L.rem);
+  long long* s_nb = (long long*)(base + L.nb);
+  double* s_dv = (double*)(base + L.dv);
+  double* s_dm = (double*)(base + L.dm);
+  const FlatOrder flat = {(int*)(base + L.ord), (int*)(base + L.tof), (int*)(base + L.tst),
+                          (int*)(base + L.cnt)};
+  unsigned* s_pw = (unsigned*)(base + L.pw);
+  unsigned* s_pn = (unsigned*)(base + L.pn);
+  int* s_rank = (int*)(base + L.rank);
+  int* s_bnd = (int*)(base + L.bnd);
+  long long* s_redg = (long long*)(base + L.redg);
+  long long* s_redc = (long long*)(base + L.redc);
+  int* s_misc = (int*)(base + L.misc);
 
   const double* d = D + (size_t)r * NM * NM;
   const double* t = T + (size_t)r * NM * NM;
@@ -240,9 +149,9 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void tw_improve_kernel(
     groups += (p == 0 || trow[p] != trow[p - 1]) ? 1 : 0;
     wait0 += strow[p] - arow[p];
   }
-  const int m = (int)team_sum<TEAM>(groups, s_redg, tid);
-  wait0 = team_sum<TEAM>(wait0, s_redg, tid);
-  if (team_sum<TEAM>(badv, s_redg, tid) != 0) return;  // not K6d's output: leave the row alone
+  const int m = (int)Tm::sum(groups, s_redg, tid);
+  wait0 = Tm::sum(wait0, s_redg, tid);
+  if (Tm::sum(badv, s_redg, tid) != 0) return;  // not K6d's output: leave the row alone
 
   // ---- gather: both quantized matrices, the per-stop vectors, the order, the trips
   for (int c = tid; c < n * n; c += TEAM) {
@@ -259,39 +168,10 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void tw_improve_kernel(
     s_qd[s] = qd;
     bigdem += qd == kBig ? 1 : 0;
   }
-  for (int p = tid; p < ns; p += TEAM) {
-    s_ord[p] = vrow[p];
-    s_bnd[p] = p > 0 && trow[p] != trow[p - 1];
-  }
-  team_sync<TEAM>();
-  for (int p = tid; p < ns; p += TEAM) {
-    int x = 0;
-    for (int y = 1; y <= p; ++y) x += s_bnd[y];
-    s_tof[p] = x;
-    if (p == 0 || s_bnd[p]) s_tst[x] = p;
-  }
-  team_sync<TEAM>();
-  for (int p = tid; p < ns; p += TEAM)
-    if (p + 1 == ns || s_bnd[p + 1]) s_cnt[s_tof[p]] = p + 1 - s_tst[s_tof[p]];
-  team_sync<TEAM>();
-  long long part = 0;
-  for (int x = tid; x < m; x += TEAM) {
-    const int st = s_tst[x], c = s_cnt[x];
-    long long L = 0, W = 0;
-    int a = 0;
-    for (int y = 0; y < c; ++y) {
-      const int b = s_ord[st + y];
-      L += sQ[a * S + b];
-      W += s_qd[b];
-      a = b;
-    }
-    L += sQ[a * S];
-    s_Lq[x] = L;
-    s_Wq[x] = W;
-    part += L;
-  }
-  const long long before = team_sum<TEAM>(part, s_redg, tid);
-  bigdem = team_sum<TEAM>(bigdem, s_redg, tid);
+  flat_build<TEAM>(flat, s_bnd, vrow, trow, ns, tid);
+  const long long part = flat_trip_sums<TEAM>(flat, m, sQ, S, s_qd, s_Lq, s_Wq, tid);
+  const long long before = Tm::sum(part, s_redg, tid);
+  bigdem = Tm::sum(bigdem, s_redg, tid);
   if (bigdem != 0 || cap_q < 0 || max_q < 0) {  // the stage is skipped
     if (tid == 0) {
       srow[0] = srow[1] = 0;
@@ -304,18 +184,14 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void tw_improve_kernel(
 
   // ---- best-improvement search
   const int ncols = ns + m + ns;  // insertion edges (one per position, one per trip), swap partners
-  int sh = 32 - __builtin_clz(ncols - 1);  // 2^sh >= ncols (ncols >= 3)
-  sh = sh > TEAM_SHIFT ? TEAM_SHIFT : sh;
-  const int CW = 1 << sh;
-  const int col0 = tid & (CW - 1), row0 = tid >> sh, rstep = TEAM >> sh;
+  const Lanes ln = Tm::split(ncols, tid);  // ncols >= 3
+  const int CW = ln.CW, col0 = ln.col0, row0 = ln.row0, rstep = ln.rstep;
   const int limit = 4 * ns;
   int cur = 0, moves = 0, rejected = 0;
   while (moves < limit) {
-    team_sync<TEAM>();
-    int* ord = s_ord + cur * V4;
-    int* tof = s_tof + cur * V4;
-    int* tst = s_tst + cur * V4;
-    int* cnt = s_cnt + cur * V4;
+    Tm::sync();
+    const FlatOrder co = flat.copy(cur, V4);
+    const int *ord = co.ord, *tof = co.tof, *tst = co.tst, *cnt = co.cnt;
     // 0. dep forwards and z backwards, one lane per trip
     for (int x = tid; x < m; x += TEAM) {
       const int st = tst[x], c = cnt[x];
@@ -339,7 +215,7 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void tw_improve_kernel(
         }
       }
     }
-    team_sync<TEAM>();
+    Tm::sync();
     // 1. per-position terms
     for (int p = tid; p < ns; p += TEAM) {
       const int s = ord[p], x = tof[p], i = p - tst[x] + 1, c = cnt[x];
@@ -361,7 +237,7 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void tw_improve_kernel(
                 (shift ? 1u << 26 : 0u);
       s_pn[p] = (unsigned)pv | ((unsigned)nx << 8);
     }
-    team_sync<TEAM>();
+    Tm::sync();
 
     // 2. the candidate scan
     long long bg = 0, bc = LLONG_MAX;
@@ -480,136 +356,31 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void tw_improve_kernel(
       }
     }
     // 3. (max gain, then min move code) over the team
-    team_best<TEAM>(bg, bc, s_redg, s_redc, tid);
+    Tm::best(bg, bc, s_redg, s_redc, tid);
     if (bg <= 0) break;
 
-    // the move, its effect on the touched trips' Lq / Wq, and the moved order in the other copy
-    const int mt = (int)(bc >> 32), mA = (int)(bc >> 24) & 255, mi = (int)(bc >> 16) & 255;
-    const int mB = (int)(bc >> 8) & 255, mj = (int)bc & 255;
-    const int nxt = cur ^ 1;
-    int* nord = s_ord + nxt * V4;
-    int* ntof = s_tof + nxt * V4;
-    int* ntst = s_tst + nxt * V4;
-    int* ncnt = s_cnt + nxt * V4;
-    const int pA = tst[mA] + mi - 1;
-    const int sA = ord[pA];
-    long long dLA, dLB, dWA, dWB;
-    if (mt != 1) {
-      const int u = mj == 0 ? 0 : ord[tst[mB] + mj - 1];
-      const int v = mj == cnt[mB] ? 0 : ord[tst[mB] + mj];
-      if (mt == 0) {
-        dLA = -s_rem[pA];
-        dLB = (long long)sQ[u * S + sA] + sQ[sA * S + v] - sQ[u * S + v];
-        dWA = -s_qd[sA];
-        dWB = s_qd[sA];
-      } else {  // one trip: its length drops by the gain
-        dLA = -bg;
-        dLB = dWA = dWB = 0;
-      }
-      // the target behind the source: the stops between move one place to the front; else one back
-      const bool fwd = mB > mA || (mB == mA && mj > mi);
-      const int dst = fwd ? tst[mB] + mj - 1 : tst[mB] + mj;
-      for (int p = tid; p < ns; p += TEAM) {
-        int src = p;
-        if (fwd) {
-          if (p >= pA && p < dst) src = p + 1;
-        } else {
-          if (p > dst && p <= pA) src = p - 1;
-        }
-        nord[p] = p == dst ? sA : ord[src];
-        ntof[p] = p == dst ? mB : tof[src];
-      }
-      for (int x = tid; x < m; x += TEAM) {
-        int st = tst[x];
-        if (mB > mA) {
-          if (x > mA && x <= mB) --st;
-        } else {
-          if (x > mB && x <= mA) ++st;
-        }
-        ntst[x] = st;
-        ncnt[x] = cnt[x] + (x == mB) - (x == mA);
-      }
-    } else {
-      const int pB = tst[mB] + mj - 1;
-      const int sB = ord[pB];
-      const unsigned pna = s_pn[pA], pnb = s_pn[pB];
-      dLA = (long long)sQ[(pna & 255) * S + sB] + sQ[sB * S + ((pna >> 8) & 255)] - s_nb[pA];
-      dLB = (long long)sQ[(pnb & 255) * S + sA] + sQ[sA * S + ((pnb >> 8) & 255)] - s_nb[pB];
-      dWA = s_qd[sB] - s_qd[sA];
-      dWB = -dWA;
-      for (int p = tid; p < ns; p += TEAM) {
-        nord[p] = p == pA ? sB : (p == pB ? sA : ord[p]);
-        ntof[p] = tof[p];
-      }
-      for (int x = tid; x < m; x += TEAM) {
-        ntst[x] = tst[x];
-        ncnt[x] = cnt[x];
-      }
-    }
-    team_sync<TEAM>();
-
-    // 4. acceptance as the greedy measures it: the touched non-empty trips, f64, in visiting order
-    const int walks = mt == 2 ? 1 : 2;
-    for (int x = 0; x < walks; ++x) {
-      const int tr = x == 0 ? mA : mB;
-      const int st = ntst[tr], c = ncnt[tr];
-      if (c == 0) continue;
-      for (int e = tid; e <= c; e += TEAM) {
-        const int a = e == 0 ? 0 : nord[st + e - 1];
-        const int b = e == c ? 0 : nord[st + e];
-        s_dv[x * V8 + e] = d[(size_t)a * NM + b];
-        if (e < c) s_dm[x * V8 + e] = dem[b];
-      }
-    }
-    team_sync<TEAM>();
-    if (tid < 2) {
-      const int c = tid < walks ? ncnt[tid == 0 ? mA : mB] : 0;
-      int ok = 1;
-      if (c > 0) {
-        const double* dv = s_dv + tid * V8;
-        const double* dm = s_dm + tid * V8;
-        double s = 0.0, load = 0.0;
-        for (int p = 0; p < c; ++p) {
-          s += dv[p];
-          load += dm[p];
-        }
-        ok = (s + dv[c] <= MD && load <= CAP) ? 1 : 0;
-      }
-      s_misc[tid] = ok;
-    }
-    team_sync<TEAM>();
-    if (!(s_misc[0] != 0 && s_misc[1] != 0)) {  // undone: the first copy stays, the search ends
+    // the moved order in the other copy, then 4. the acceptance walks of the touched trips; an
+    // emptied trip is not walked.  Undone: the first copy stays, the search ends.
+    const Move mv = decode_move(bc);
+    const FlatOrder nx = flat.copy(cur ^ 1, V4);
+    const MoveDelta dl = flat_write_move<TEAM>(co, nx, mv, bg, ns, m, sQ, S, s_qd, s_rem, s_nb, s_pn, tid);
+    Tm::sync();
+    if (!flat_accept<TEAM, true>(nx, mv, d, dem, NM, MD, CAP, s_dv, s_dm, V8, s_misc, tid)) {
       rejected = 1;
       break;
     }
-    if (tid == 0) {
-      s_Lq[mA] += dLA;
-      s_Wq[mA] += dWA;
-      if (mt != 2) {
-        s_Lq[mB] += dLB;
-        s_Wq[mB] += dWB;
-      }
-    }
-    cur = nxt;
+    if (tid == 0) flat_commit(s_Lq, s_Wq, mv, dl);
+    cur ^= 1;
     ++moves;
   }
-  team_sync<TEAM>();
+  Tm::sync();
 
   // ---- the non-empty trips, compacted in their order, with their schedule
-  const int* ord = s_ord + cur * V4;
-  const int* tof = s_tof + cur * V4;
-  const int* tst = s_tst + cur * V4;
-  const int* cnt = s_cnt + cur * V4;
+  const FlatOrder fin = flat.copy(cur, V4);
+  const int *ord = fin.ord, *tof = fin.tof, *tst = fin.tst, *cnt = fin.cnt;
   if (tid == 0) {
-    int k = 0;
-    long long after = 0;
-    for (int x = 0; x < m; ++x) {
-      s_rank[x] = k;
-      if (cnt[x] > 0) {
-        ++k;
-        after += s_Lq[x];
-      }
-    }
+    long long after;
+    const int k = flat_rank(cnt, s_Lq, m, s_rank, after);
     ntrips[r] = k;
     srow[0] = moves;
     srow[1] = rejected;
@@ -633,7 +404,7 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void tw_improve_kernel(
       a = b;
     }
   }
-  team_sync<TEAM>();
+  Tm::sync();
   long long wait_part = 0;
   for (int p = tid; p < ns; p += TEAM) {
     vrow[p] = ord[p];
@@ -642,7 +413,7 @@ __global__ __launch_bounds__(TEAM == 64 ? 256 : TEAM) void tw_improve_kernel(
     strow[p] = s_dep[p];
     wait_part += s_dep[p] - s_z[p];
   }
-  const long long waiting = team_sum<TEAM>(wait_part, s_redg, tid);
+  const long long waiting = Tm::sum(wait_part, s_redg, tid);
   if (tid == 0) srow[6] = waiting;
 }
 
@@ -653,34 +424,11 @@ hipError_t launch_tw_improve(const double* D, const double* T, const int* npts, 
                              const long long* close, const long long* service, const unsigned char* flag,
                              int R, int NM, int* visit, int* trip_of, int* ntrips, const int* status,
                              long long* arrival, long long* start, long long* stats, hipStream_t stream) {
-  if (R == 0) return hipSuccess;
-  if (NM < 1 || NM > 4096) return hipErrorInvalidValue;
-  static_assert(twi_team_bytes(kMaxStops) <= 160 * 1024, "a row's LDS must fit a CU");
-  static_assert(4 * twi_team_bytes(kSmallStops) <= 64 * 1024, "the small tier stays in the default LDS size");
-  // small tier: rows of at most 32 stops, a wavefront each
-  {
-    const int kc = NM - 1 < kSmallStops ? (NM - 1 < 1 ? 1 : NM - 1) : kSmallStops;
-    const size_t lds = 4 * twi_team_bytes(kc);
-    hipLaunchKernelGGL(tw_improve_kernel<64>, dim3((R + 3) / 4), dim3(256), lds, stream, D, T, npts, demand,
-                       cap, maxd, open, close, service, flag, R, NM, kc, visit, trip_of, ntrips, status,
-                       arrival, start, stats);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  if (NM - 1 <= kSmallStops) return hipSuccess;
-  // large tier: a 1024-thread workgroup each; both int32 matrices of 128 stops (2 x 66.6 KB) and the
-  // per-stop / per-trip arrays need the opt-in LDS size
-  const int kc = NM - 1 < kMaxStops ? NM - 1 : kMaxStops;
-  const size_t lds = twi_team_bytes(kc);
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)tw_improve_kernel<kLargeTeam>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(tw_improve_kernel<kLargeTeam>, dim3(R), dim3(kLargeTeam), lds, stream, D, T, npts,
-                     demand, cap, maxd, open, close, service, flag, R, NM, kc, visit, trip_of, ntrips,
-                     status, arrival, start, stats);
-  return hipGetLastError();
+  // both int32 matrices of 128 stops (2 x 66.6 KB) and the per-stop / per-trip arrays
+  return team::launch_two_tiers<TwImproveLds>(tw_improve_kernel<64>, tw_improve_kernel<team::kLargeTeam>, R, NM,
+                                              stream, D, T, npts, demand, cap, maxd, open, close, service,
+                                              flag, R, NM, visit, trip_of, ntrips, status, arrival, start,
+                                              stats);
 }
 
 }  // namespace rt
