@@ -602,6 +602,47 @@ std::vector<torch::Tensor> route_tw_trips(torch::Tensor D, torch::Tensor T, torc
   return {visit, trip_of, ntrips, status, arrival, start, stats};
 }
 
+// K6f: rows with flag != 0 are planned as shipment requests (routing/shipments.py): plain stops and
+// pickup -> delivery pairs under their time windows.  pickup_from i32 [R,NM]: per point the point
+// index of its pickup, negative for none.  Outputs and statuses as route_tw_trips; status 3: a
+// malformed pickup_from.
+std::vector<torch::Tensor> route_pd_trips(torch::Tensor D, torch::Tensor T, torch::Tensor npts,
+                                          torch::Tensor demand, torch::Tensor cap, torch::Tensor maxd,
+                                          torch::Tensor open, torch::Tensor close, torch::Tensor service,
+                                          torch::Tensor pickup_from, torch::Tensor flag) {
+  for (auto* t : {&D, &T, &npts, &demand, &cap, &maxd, &open, &close, &service, &pickup_from, &flag})
+    check_dev(*t, "route tensor");
+  check_route_D(D, &T);
+  const int R = (int)D.size(0), NM = (int)D.size(1);
+  TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
+  check_route_vec(npts, torch::kInt32, R, "npts");
+  check_route_rows({&demand}, torch::kFloat64, R, NM, "demand");
+  check_route_vec(cap, torch::kFloat64, R, "cap");
+  check_route_vec(maxd, torch::kFloat64, R, "maxd");
+  check_route_rows({&open, &close, &service}, torch::kInt64, R, NM, "open, close and service", " (milliseconds)");
+  check_route_rows({&pickup_from}, torch::kInt32, R, NM, "pickup_from");
+  check_route_vec(flag, torch::kUInt8, R, "flag");
+  const c10::DeviceGuard guard(D.device());
+  auto iopt = D.options().dtype(torch::kInt32);
+  auto lopt = D.options().dtype(torch::kInt64);
+  auto visit = torch::full({R, NM}, -1, iopt);
+  auto trip_of = torch::full({R, NM}, -1, iopt);
+  auto ntrips = torch::zeros({R}, iopt);
+  auto status = torch::zeros({R}, iopt);
+  auto arrival = torch::full({R, NM}, -1, lopt);
+  auto start = torch::full({R, NM}, -1, lopt);
+  auto stats = torch::zeros({R, 4}, lopt);
+  RT_CHECK_HIP(rt::launch_pd_trips(
+      D.data_ptr<double>(), T.data_ptr<double>(), npts.data_ptr<int>(), demand.data_ptr<double>(),
+      cap.data_ptr<double>(), maxd.data_ptr<double>(), (const long long*)open.data_ptr<int64_t>(),
+      (const long long*)close.data_ptr<int64_t>(), (const long long*)service.data_ptr<int64_t>(),
+      pickup_from.data_ptr<int>(), flag.data_ptr<uint8_t>(), R, NM, visit.data_ptr<int>(),
+      trip_of.data_ptr<int>(), ntrips.data_ptr<int>(), status.data_ptr<int>(),
+      (long long*)arrival.data_ptr<int64_t>(), (long long*)start.data_ptr<int64_t>(),
+      (long long*)stats.data_ptr<int64_t>(), cur_stream(D)));
+  return {visit, trip_of, ntrips, status, arrival, start, stats};
+}
+
 // K6e on K6d's own outputs: visit / trip_of / ntrips / arrival / start are rewritten in place for
 // rows with flag != 0 and status == 0 (routing/tw_improve.py).  Returns stats i64 [R,7] = moves,
 // rejected, trips_before, trips_after, len_before_q, len_after_q, waiting_q (0 for rows left alone).
@@ -1706,6 +1747,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K6d: cheapest-insertion trips under time windows and service times for the flagged rows",
         py::arg("D"), py::arg("T"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"),
         py::arg("open"), py::arg("close"), py::arg("service"), py::arg("flag"));
+  m.def("route_pd_trips", &route_pd_trips,
+        "K6f: cheapest insertion of plain stops and pickup -> delivery pairs under time windows for the flagged rows",
+        py::arg("D"), py::arg("T"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"),
+        py::arg("open"), py::arg("close"), py::arg("service"), py::arg("pickup_from"), py::arg("flag"));
   m.def("route_tw_improve", &route_tw_improve,
         "K6e: window-aware relocate / swap on K6d's outputs (rewritten in place); returns stats [R,7]",
         py::arg("D"), py::arg("T"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"),

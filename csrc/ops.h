@@ -242,6 +242,18 @@ hipError_t launch_tw_trips(const double* D, const double* T, const int* npts, co
                            int R, int NM, int* visit, int* trip_of, int* ntrips, int* status,
                            long long* arrival, long long* start, long long* stats, hipStream_t stream);
 
+// ---- K6f cheapest insertion of plain stops and pickup -> delivery pairs : route_pd.hip ----
+// Rows with flag != 0 are planned (routing/shipments.py); inputs and outputs as launch_tw_trips, and
+// pickup_from [R, NM] int32 per point (column 0 ignored): the point index of a delivery's pickup,
+// negative for none.  status 3: a malformed pickup_from (not another stop of the row, itself a
+// delivery, or the pickup of two deliveries).  Rows with flag == 0 are not touched.
+hipError_t launch_pd_trips(const double* D, const double* T, const int* npts, const double* demand,
+                           const double* cap, const double* maxd, const long long* open,
+                           const long long* close, const long long* service, const int* pickup_from,
+                           const unsigned char* flag, int R, int NM, int* visit, int* trip_of, int* ntrips,
+                           int* status, long long* arrival, long long* start, long long* stats,
+                           hipStream_t stream);
+
 // ---- K6e window-aware relocate / swap on K6d's outputs : route_tw_improve.hip ----
 // visit, trip_of, ntrips, arrival and start are rewritten in place for rows with flag != 0 and
 // status == 0 (routing/tw_improve.py; still grouped by trip, trip indices compacted) and their

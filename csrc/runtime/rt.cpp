@@ -497,6 +497,48 @@ py::tuple tw_trips(py::array_t<double, py::array::c_style | py::array::forcecast
   return py::make_tuple(trips, sched, s);
 }
 
+// ------------------------------------------------------------------ pickup-and-delivery pairs (shipments.py)
+// tw_trips' arguments and pickup_from [n1] (the point index of a delivery's pickup, negative: none)
+// -> what tw_trips returns
+py::tuple pd_trips(py::array_t<double, py::array::c_style | py::array::forcecast> D,
+                   py::array_t<double, py::array::c_style | py::array::forcecast> T, std::vector<double> demand,
+                   double cap, double maxd, std::vector<long long> open, std::vector<long long> close,
+                   std::vector<long long> sv, std::vector<int> pickup_from) {
+  if (D.ndim() != 2 || D.shape(0) != D.shape(1)) throw std::invalid_argument("D must be square");
+  const int n1 = (int)D.shape(0);
+  if (T.ndim() != 2 || T.shape(0) != n1 || T.shape(1) != n1) throw std::invalid_argument("T must have D's shape");
+  if (n1 < 1 || n1 - 1 > rtr::kImproveMaxStops) throw std::invalid_argument("at most 128 stops with shipments");
+  if ((int)demand.size() != n1 || (int)open.size() != n1 || (int)close.size() != n1 || (int)sv.size() != n1 ||
+      (int)pickup_from.size() != n1)
+    throw std::invalid_argument("demand, open_q, close_q, sv_q and pickup_from hold one entry per point");
+  std::vector<int> kind, mate;
+  if (!rtr::pd_kinds(pickup_from, n1, kind, mate))
+    throw std::invalid_argument("pickup_from must name another stop that is no delivery and no other delivery's pickup");
+  const std::vector<double> d(D.data(), D.data() + (size_t)n1 * n1), t(T.data(), T.data() + (size_t)n1 * n1);
+  std::vector<std::vector<int>> trips;
+  std::vector<std::vector<long long>> arr, sta;
+  std::vector<int> bad;
+  rtr::TwStats st;
+  if (!rtr::pd_trips(d, t, n1, demand, cap, maxd, open, close, sv, kind, mate, trips, arr, sta, bad, st))
+    return py::make_tuple(py::none(), bad, py::none());
+  py::list sched;
+  for (size_t k = 0; k < trips.size(); ++k) {
+    py::list one;
+    for (size_t i = 0; i < arr[k].size(); ++i) {
+      const int s = trips[k][i + 1];
+      one.append(py::make_tuple(s, arr[k][i], sta[k][i], sta[k][i] + sv[s]));
+    }
+    sched.append(one);
+  }
+  py::dict s;
+  s["insertions"] = st.insertions;
+  s["rejected"] = st.rejected;
+  s["trips"] = st.trips;
+  s["len_q"] = st.len_q;
+  s["waiting_q"] = st.waiting_q;
+  return py::make_tuple(trips, sched, s);
+}
+
 // ------------------------------------------------------------------ window-aware local search (tw_improve.py)
 // (D, T [n1, n1], trips, demand [n1], cap, max_dist, open_q, close_q, sv_q [n1]) -> (trips, schedule,
 // {moves, rejected, trips_before, trips_after, len_before_q, len_after_q, waiting_q})
@@ -566,6 +608,8 @@ PYBIND11_MODULE(_rt, m) {
         py::arg("max_dist"), py::arg("move_cap") = py::none());
   m.def("tw_trips", &tw_trips, py::arg("D"), py::arg("T"), py::arg("demand"), py::arg("cap"), py::arg("max_dist"),
         py::arg("open_q"), py::arg("close_q"), py::arg("sv_q"));
+  m.def("pd_trips", &pd_trips, py::arg("D"), py::arg("T"), py::arg("demand"), py::arg("cap"), py::arg("max_dist"),
+        py::arg("open_q"), py::arg("close_q"), py::arg("sv_q"), py::arg("pickup_from"));
   m.def("tw_improve", &tw_improve, py::arg("D"), py::arg("T"), py::arg("trips"), py::arg("demand"), py::arg("cap"),
         py::arg("max_dist"), py::arg("open_q"), py::arg("close_q"), py::arg("sv_q"));
   m.def("astar_batch", &astar_batch, py::arg("indptr"), py::arg("indices"), py::arg("cost"),

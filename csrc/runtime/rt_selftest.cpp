@@ -1124,6 +1124,133 @@ static void threaded_pack_format(int n_items) {
   CHECK(recs[n_items - 1].distance_m == (float)(1000 + n_items - 1), "threaded pack record");
 }
 
+// route_core.h pd_trips (instances as in fuzz_tw, half as many, with random pickup -> delivery pairs):
+// either some stop is reported infeasible alone (a pair with both indices) or every stop is routed
+// exactly once, a pair in one trip with its pickup first, every trip re-simulates as feasible in time
+// and in its integer load profile against the fixed-point capacity, and both float walks hold
+static void fuzz_pd(std::mt19937_64& rng, int iters) {
+  for (int it = 0; it < iters / 200; ++it) {
+    const int n1 = 1 + (int)(rng() % 34);
+    std::vector<double> d((size_t)n1 * n1, 0.0), t((size_t)n1 * n1, 0.0), dem(n1, 0.0);
+    for (int a = 0; a < n1; ++a)
+      for (int b = 0; b < n1; ++b)
+        if (a != b) {
+          d[(size_t)a * n1 + b] = 100.0 + (double)(rng() % 1000000) / 37.0;
+          t[(size_t)a * n1 + b] = 10.0 + (double)(rng() % 100000) / 53.0;
+        }
+    if (rng() % 3 == 0 && n1 > 4) {
+      const double bad[6] = {NAN, INFINITY, -5.0, 2147483.647, 3e9, 1e300};
+      for (int x = 0; x < 6; ++x) {
+        std::vector<double>& m = rng() % 2 ? d : t;
+        const int a = rng() % 8 == 0 ? 0 : 1 + (int)(rng() % (n1 - 1)), b = 1 + (int)(rng() % (n1 - 1));
+        if (a != b) m[(size_t)a * n1 + b] = bad[rng() % 6];
+      }
+    }
+    std::vector<long long> open(n1, 0), close(n1, rtr::kExchangeUnbounded), sv(n1, 0);
+    for (int s = 1; s < n1; ++s) {
+      dem[s] = (double)(1 + rng() % 3);
+      if (rng() % 10 < 5) {
+        open[s] = (long long)(rng() % 20000000);
+        close[s] = open[s] + (long long)(rng() % 3 == 0 ? 0 : rng() % 8000000);
+        if (rng() % 4 == 0) open[s] = 0;
+      }
+      if (rng() % 2) sv[s] = (long long)(rng() % 600000);
+    }
+    // about half of the stops in pairs: consecutive entries of a shuffled order
+    std::vector<int> order, pf(n1, -1);
+    for (int s = 1; s < n1; ++s) order.push_back(s);
+    for (size_t x = order.size(); x > 1; --x) std::swap(order[x - 1], order[rng() % x]);
+    for (size_t x = 0; x < order.size() / 4; ++x) pf[order[2 * x + 1]] = order[2 * x];
+    const bool odd_demand = rng() % 16 == 0 && n1 > 1;  // a negative demand passes the float test alone
+    if (odd_demand) dem[1 + rng() % (n1 - 1)] = rng() % 2 ? NAN : -1.0;
+    const bool free_run = rng() % 3 == 0;
+    const double cap = free_run ? 9e12 : (rng() % 16 == 0 ? NAN : (double)(3 + rng() % 30));
+    const double maxd = free_run ? 9e12 : (rng() % 16 == 0 ? -1.0 : 60000.0 + (double)(rng() % 400000));
+    std::vector<int> kind, mate;
+    CHECK(rtr::pd_kinds(pf, n1, kind, mate), "pd_kinds refused well-formed pairs");
+    {  // malformed: a chain and a shared pickup
+      std::vector<int> k2, m2, bad_pf = pf;
+      if (n1 > 3) {
+        bad_pf.assign(n1, -1);
+        bad_pf[1] = 2;
+        bad_pf[2] = 3;
+        CHECK(!rtr::pd_kinds(bad_pf, n1, k2, m2), "pd_kinds took a chain");
+        bad_pf[2] = -1;
+        bad_pf[3] = 2;
+        CHECK(!rtr::pd_kinds(bad_pf, n1, k2, m2), "pd_kinds took a shared pickup");
+      }
+    }
+    std::vector<std::vector<int>> trips;
+    std::vector<std::vector<long long>> arr, sta;
+    std::vector<int> bad;
+    rtr::TwStats st;
+    if (!rtr::pd_trips(d, t, n1, dem, cap, maxd, open, close, sv, kind, mate, trips, arr, sta, bad, st)) {
+      CHECK(!bad.empty() && trips.empty(), "pd_trips failed without naming a stop");
+      for (size_t x = 0; x < bad.size(); ++x) {
+        CHECK(bad[x] >= 0 && bad[x] < n1 - 1 && (x == 0 || bad[x] > bad[x - 1]), "pd_trips infeasible index %d", bad[x]);
+        const int s = bad[x] + 1;
+        if (s >= 1 && s < n1 && kind[s] != rtr::kPdPlain)
+          CHECK(std::find(bad.begin(), bad.end(), mate[s] - 1) != bad.end(), "pd_trips reported half a pair (%d)", s);
+      }
+      continue;
+    }
+    long long cap_q = -1;
+    if (!rtr::exchange_limit(cap, cap_q)) cap_q = -1;
+    std::vector<int> seen(n1, 0), trip_of(n1, -1), pos_of(n1, -1);
+    long long len = 0, waiting = 0, units = 0;
+    CHECK(trips.size() == arr.size() && trips.size() == sta.size() && st.trips == (long long)trips.size(), "pd_trips trip counts");
+    for (size_t k = 0; k < trips.size(); ++k) {
+      const std::vector<int>& tr = trips[k];
+      CHECK(tr.size() >= 3 && tr.front() == 0 && tr.back() == 0, "pd_trips broke a trip's ends");
+      CHECK(arr[k].size() + 2 == tr.size() && sta[k].size() + 2 == tr.size(), "pd_trips schedule length");
+      long long clock = 0, load = 0, top = 0;
+      bool ok = true;
+      for (size_t p = 1; p + 1 < tr.size(); ++p)
+        if (tr[p] >= 1 && tr[p] < n1 && kind[tr[p]] == rtr::kPdPlain) load += rtr::improve_q(dem[tr[p]]);
+      top = load;
+      for (size_t p = 0; p + 1 < tr.size(); ++p) {
+        const int a = tr[p], b = tr[p + 1];
+        if (a < 0 || a >= n1 || b < 0 || b >= n1) { ok = false; break; }
+        const long long q = rtr::tw_q(d[(size_t)a * n1 + b]), qt = rtr::tw_q(t[(size_t)a * n1 + b]);
+        ok = ok && q < rtr::kImproveBig && qt < rtr::kImproveBig;
+        len += q;
+        if (b == 0) break;
+        ++seen[b];
+        trip_of[b] = (int)k;
+        pos_of[b] = (int)p + 1;
+        units += kind[b] != rtr::kPdDelivery;
+        const long long ar = clock + qt, s0 = std::max(ar, open[b]);
+        ok = ok && s0 <= close[b] && p < arr[k].size() && arr[k][p] == ar && sta[k][p] == s0;
+        waiting += s0 - ar;
+        clock = s0 + sv[b];
+        load += kind[b] == rtr::kPdPickup ? rtr::improve_q(dem[mate[b]]) : -rtr::improve_q(dem[b]);
+        top = std::max(top, load);
+      }
+      CHECK(ok, "pd_trips built a trip that does not re-simulate as feasible");
+      // a seed is admitted by the float test alone; every longer trip passed the integer profile
+      if (!odd_demand && (tr.size() > 4 || (tr.size() == 4 && kind[tr[1]] == rtr::kPdPlain)))
+        CHECK(top <= cap_q, "pd_trips overloaded a trip: %lld > %lld", top, cap_q);
+      double s = 0.0;
+      const int kk = (int)tr.size() - 2;
+      for (int p = 0; p < kk; ++p) s += d[(size_t)tr[p] * n1 + tr[p + 1]];
+      CHECK(s + d[(size_t)tr[kk] * n1] <= maxd && rtr::pd_load_feasible(dem, kind, mate, tr, cap),
+            "pd_trips kept a trip that fails the float walks");
+    }
+    bool once = true, paired = true;
+    for (int s = 1; s < n1; ++s) {
+      once = once && seen[s] == 1;
+      if (kind[s] == rtr::kPdPickup)
+        paired = paired && trip_of[s] == trip_of[mate[s]] && pos_of[s] < pos_of[mate[s]];
+    }
+    CHECK(once, "pd_trips lost or repeated a stop");
+    CHECK(paired, "pd_trips split a pair or delivered before the pickup");
+    CHECK(len == st.len_q && waiting == st.waiting_q, "pd_trips statistics: len %lld / %lld, waiting %lld / %lld", st.len_q, len,
+          st.waiting_q, waiting);
+    CHECK(st.insertions + st.trips == units, "pd_trips: %lld insertions + %lld trips != %lld units", st.insertions, st.trips,
+          units);
+  }
+}
+
 int main(int argc, char** argv) {
   const int iters = argc > 1 ? std::atoi(argv[1]) : 20000;
   std::mt19937_64 rng(argc > 2 ? std::strtoull(argv[2], nullptr, 10) : 1234);
@@ -1142,6 +1269,7 @@ int main(int argc, char** argv) {
   fuzz_mm_viterbi(rng, iters);
   fuzz_avoid_mask(rng, iters);
   fuzz_tw_improve(rng, iters);
+  fuzz_pd(rng, iters);
   store_while_reading();
   threaded_pack_format(20000);
   std::printf("rt_selftest: %d iterations, %d failures\n", iters, g_fail);

@@ -12,6 +12,9 @@ relocate / swap search of :mod:`routing.exchange` between two such passes (on a 
 Requests given ``time_windows`` are planned by the cheapest insertion of :mod:`routing.timewindows`
 instead (on a GPU one launch, K6d, over the flagged rows only); per-request ``tw_improve`` flags add
 the window-aware local search of :mod:`routing.tw_improve` on those rows (on a GPU one more launch, K6e).
+A ``time_windows`` entry of four, ``pickup_from`` per point behind the windows, makes its row a
+shipment row: pickup -> delivery pairs planned by :mod:`routing.shipments` (on a GPU one launch, K6f,
+over those rows only); such a row is none of K6b's, K6c's, K6d's or K6e's.
 Sharding over several GPUs is done by
 :class:`routing.route_batcher.RouteBatcher` (one worker thread per device, no collective).
 """
@@ -27,6 +30,7 @@ from .greedy import InfeasibleStops, greedy_trips
 from .exchange import UNBOUNDED, improve_exchange_trips
 from .improve import improve_trips
 from .providers import haversine_matrix
+from .shipments import pd_trips
 from .timewindows import MAX_STOPS as TW_MAX_STOPS, tw_trips
 from .tw_improve import STAT_KEYS as TWI_STAT_KEYS, tw_improve_trips
 
@@ -119,19 +123,45 @@ def pack_time_windows(requests: Sequence[Dict[str, Any]], time_windows: Sequence
         if tw is None:
             continue
         n = 1 + len(r["destination_points"])
-        if n - 1 > TW_MAX_STOPS or any(len(v) != n for v in tw):
+        if n - 1 > TW_MAX_STOPS or len(tw) not in (3, 4) or any(len(v) != n for v in tw):
             raise ValueError(f"time_windows[{k}] must hold one entry per point, at most {TW_MAX_STOPS} stops")
         flags[k] = 1
-        op[k, :n], cl[k, :n], sv[k, :n] = tw
+        op[k, :n], cl[k, :n], sv[k, :n] = tw[:3]
         drv = r.get("driver_details") or {}
         profile = profile_for(drv.get("vehicle_type") if isinstance(drv, dict) else None)
         speed[k] = PROFILE_SPEED_MPS.get(profile, PROFILE_SPEED_MPS["driving-car"])
     return op, cl, sv, flags, speed
 
 
-def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw, twi=None):
+def pack_shipments(time_windows: Sequence[Any], nm: int):
+    """The shipment rows of ``time_windows`` (entries of four: ``pickup_from`` per point behind the
+    windows, :func:`shipments.parse_shipments`): ``(pickup_from`` int32 [R, nm], -1 where there is
+    none, ``flags`` uint8 [R])."""
+    R = len(time_windows)
+    pf = np.full((R, nm), -1, dtype=np.int32)
+    flags = np.zeros(R, dtype=np.uint8)
+    for k, tw in enumerate(time_windows):
+        if tw is not None and len(tw) == 4:
+            flags[k] = 1
+            pf[k, :len(tw[3])] = tw[3]
+    return pf, flags
+
+
+def _pd_device(C, t, D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, pd):
+    """K6f over the shipment rows: K6d's seven outputs, on the host."""
+    pf, pdf = pd
+    out = C.route_pd_trips(D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, t(pf, torch.int32),
+                           t(pdf, torch.uint8))
+    out = [c.cpu().numpy() for c in out]
+    if (out[3][pdf != 0] == 3).any():
+        raise ValueError("pickup_from must name another stop that is no delivery and no other delivery's pickup")
+    return out
+
+
+def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw, twi=None, pd=None):
     """K6d over the flagged rows: ``{row: trips or InfeasibleStops}``, ``{row: (schedule, stats)}``.
-    ``twi``: uint8 flags of the rows whose trips K6e then improves (``stats["search"]``)."""
+    ``twi``: uint8 flags of the rows whose trips K6e then improves (``stats["search"]``).  ``pd``:
+    ``(pickup_from, flags)`` of :func:`pack_shipments`; those rows are K6f's, not K6d's or K6e's."""
     op, cl, sv, twf, speed = tw
     if T is None:
         # one IEEE division per entry, as HaversineProvider.time_matrix does it on the host
@@ -140,13 +170,26 @@ def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw, twi=None):
         T = t(np.ascontiguousarray(T, dtype=np.float64))
     T = T.contiguous()
     op_t, cl_t, sv_t = t(op, torch.int64), t(cl, torch.int64), t(sv, torch.int64)
-    out = C.route_tw_trips(D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, t(twf, torch.uint8))
-    search = None
-    if twi is not None and (twi & twf).any():
-        # K6e rewrites K6d's outputs in place for the asking rows; K6d's own statistics stay
-        search = C.route_tw_improve(D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, *out[:6],
-                                    t(twi & twf, torch.uint8)).cpu().numpy()
-    visit, trip_of, ntrips, status, arr, start, stats = (c.cpu().numpy() for c in out)
+    pdf = pd[1] if pd is not None else np.zeros_like(twf)
+    k6d = twf & ~pdf & 1
+    out = search = None
+    if k6d.any():
+        out = C.route_tw_trips(D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, t(k6d, torch.uint8))
+        if twi is not None and (twi & k6d).any():
+            # K6e rewrites K6d's outputs in place for the asking rows; K6d's own statistics stay
+            search = C.route_tw_improve(D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, *out[:6],
+                                        t(twi & k6d, torch.uint8)).cpu().numpy()
+            twi = twi & k6d
+        out = [c.cpu().numpy() for c in out]
+    if pdf.any():
+        # K6f's rows beside K6d's (a batch without shipment rows launches nothing more)
+        ship = _pd_device(C, t, D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, pd)
+        if out is None:
+            out = ship
+        else:
+            for a, b in zip(out, ship):
+                a[pdf != 0] = b[pdf != 0]
+    visit, trip_of, ntrips, status, arr, start, stats = out
     rows = np.flatnonzero(twf)
     if (status[rows] > 1).any():
         raise ValueError(f"time-window rows take at most {TW_MAX_STOPS} stops")
@@ -172,7 +215,7 @@ def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw, twi=None):
 def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device,
                          D: Optional[np.ndarray] = None, improve: Optional[Sequence[Any]] = None,
                          exchange: Optional[Sequence[Any]] = None, tw=None, T: Optional[np.ndarray] = None,
-                         tw_improve: Optional[Sequence[Any]] = None):
+                         tw_improve: Optional[Sequence[Any]] = None, pd=None):
     # K6 indexes its LDS order / visited arrays by stop number: a request longer than the padded
     # width would write past them, so it is refused here, before anything reaches the device
     nm = int(D.shape[1]) if D is not None else int(np.shape(lat)[1])
@@ -214,7 +257,7 @@ def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device
         twres: List[Any] = [None] * len(n)
         if tw[3].any():
             planned, sched = _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw,
-                                        _flags(tw_improve, len(n)))
+                                        _flags(tw_improve, len(n)), pd)
             for k, v in planned.items():
                 out[k] = v
                 twres[k] = sched.get(k)
@@ -242,7 +285,7 @@ def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device
 def batched_trips_cpu(lat, lon, dem, npts, cap, maxd, circuity: float,
                       D: Optional[np.ndarray] = None, improve: Optional[Sequence[Any]] = None,
                       exchange: Optional[Sequence[Any]] = None, tw=None, T: Optional[np.ndarray] = None,
-                      tw_improve: Optional[Sequence[Any]] = None):
+                      tw_improve: Optional[Sequence[Any]] = None, pd=None):
     out: List[TripsOrError] = []
     flags, xflags = _both_flags(improve, exchange, len(npts))
     twi = _flags(tw_improve, len(npts))
@@ -256,9 +299,14 @@ def batched_trips_cpu(lat, lon, dem, npts, cap, maxd, circuity: float,
             # the reference of K6d (routing/timewindows.py); improve / exchange are ignored
             sec = T[k, :n, :n] if T is not None else np.asarray(d, dtype=np.float64) / tw[4][k]
             try:
-                trips, sched, tst = tw_trips(d, sec, dem[k, :n].tolist(), float(cap[k]), float(maxd[k]),
-                                             tw[0][k, :n], tw[1][k, :n], tw[2][k, :n])
-                if twi is not None and twi[k]:
+                if pd is not None and pd[1][k]:
+                    # the reference of K6f (routing/shipments.py); tw_improve is ignored as well
+                    trips, sched, tst = pd_trips(d, sec, dem[k, :n].tolist(), float(cap[k]), float(maxd[k]),
+                                                 tw[0][k, :n], tw[1][k, :n], tw[2][k, :n], pd[0][k, :n].tolist())
+                else:
+                    trips, sched, tst = tw_trips(d, sec, dem[k, :n].tolist(), float(cap[k]), float(maxd[k]),
+                                                 tw[0][k, :n], tw[1][k, :n], tw[2][k, :n])
+                if twi is not None and twi[k] and not (pd is not None and pd[1][k]):
                     # the reference of K6e (routing/tw_improve.py) on the insertion's trips
                     trips, sched, search = tw_improve_trips(d, sec, trips, dem[k, :n].tolist(), float(cap[k]),
                                                             float(maxd[k]), tw[0][k, :n], tw[1][k, :n], tw[2][k, :n])
@@ -306,7 +354,12 @@ def batched_trips(requests: Sequence[Dict[str, Any]], circuity: float = 1.3,
 
     ``tw_improve``: one flag per request, honoured only on time-window rows: their trips are improved
     by the window-aware local search of :mod:`routing.tw_improve` (on a GPU one more launch, K6e) and
-    ``statistics["search"]`` holds what it did; an unflagged row's entry is as without the argument."""
+    ``statistics["search"]`` holds what it did; an unflagged row's entry is as without the argument.
+
+    A ``time_windows`` entry ``(open_q, close_q, sv_q, pickup_from)`` (``pickup_from`` as
+    :func:`shipments.parse_shipments` returns it) is a shipment request: planned by
+    :mod:`routing.shipments` (on a GPU one launch, K6f); ``improve`` / ``exchange`` / ``tw_improve``
+    are ignored on it and its ``tw[k]`` is shaped like a time-window row's."""
     if time_windows is not None and (D is None) != (T is None):
         raise ValueError("time windows on given matrices need both D (metres) and T (seconds)")
     if not requests:
@@ -314,12 +367,14 @@ def batched_trips(requests: Sequence[Dict[str, Any]], circuity: float = 1.3,
             return [], [], []
         return [] if improve is None and exchange is None else ([], [])
     packed = pack_requests(requests)
-    tw = None
+    tw = pd = None
     if time_windows is not None:
         nm = int(D.shape[1]) if D is not None else int(packed[0].shape[1])
         tw = pack_time_windows(requests, time_windows, nm)
+        pd = pack_shipments(time_windows, nm)
+        pd = pd if pd[1].any() else None
     if device is not None and torch.device(device).type == "cuda":
         return batched_trips_device(*packed, circuity=circuity, device=device, D=D, improve=improve,
-                                    exchange=exchange, tw=tw, T=T, tw_improve=tw_improve)
+                                    exchange=exchange, tw=tw, T=T, tw_improve=tw_improve, pd=pd)
     return batched_trips_cpu(*packed, circuity=circuity, D=D, improve=improve, exchange=exchange, tw=tw, T=T,
-                             tw_improve=tw_improve)
+                             tw_improve=tw_improve, pd=pd)

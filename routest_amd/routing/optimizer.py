@@ -22,6 +22,9 @@ are routed, and ``properties.improvement`` reports what it did.  Single-destinat
 of :mod:`routing.exchange` between two such passes; the answer may then hold fewer trips.
 ``"tw_improve": true`` (same rule) on a time-window request improves the cheapest insertion's trips
 by the window-aware local search of :mod:`routing.tw_improve`; any other request ignores it.
+A destination carrying ``"pickup_from": p`` makes a multi-stop request a shipment request
+(:mod:`routing.shipments`): pickup -> delivery pairs and plain stops planned by cheapest insertion
+of units under the windows; ``improve`` / ``exchange`` / ``tw_improve`` are ignored there.
 The batched GPU path for many concurrent requests (K5 + K6) is :func:`optimize_many`.
 """
 from __future__ import annotations
@@ -36,6 +39,8 @@ from .improve import improve_trips, improvement_properties, wants_improve
 from .providers import ProviderError, _bbox, profile_for
 from .timewindows import (NEEDS_MATRIX_TIMES, parse_time_windows, schedule_properties, tw_trips,
                           wants_time_windows)
+from .shipments import (NEEDS_MATRIX_TIMES as PD_NEEDS_MATRIX_TIMES, parse_shipments, pd_trips,
+                        shipment_properties, wants_shipments)
 from .tw_improve import tw_improve_trips, wants_tw_improve
 
 
@@ -119,30 +124,36 @@ def assemble_trips(provider, all_points: List[Dict[str, Any]], trips: List[List[
 def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, Any],
                trips: Optional[List[List[int]]] = None, ctx=None, improve: bool = False,
                improvement: Optional[Dict[str, int]] = None, exchange: bool = False,
-               tw=None, tw_result=None, tw_improve: bool = False) -> Dict[str, Any]:
+               tw=None, tw_result=None, tw_improve: bool = False, pd=None) -> Dict[str, Any]:
     """``improve``: re-sequence the trips built here (routing/improve.py); ``exchange``: also move
     stops between them (routing/exchange.py; it implies ``improve``).  Trips given by the caller
     are taken as they are; ``improvement`` holds their statistics if they were improved.
     ``tw``: the request's ``(open_q, close_q, sv_q)`` (routing/timewindows.py): the trips are built
     by cheapest insertion under the windows, ``improve`` / ``exchange`` are ignored and the response
     carries ``schedule`` / ``time_windows``; ``tw_result``: the ``(schedule, statistics)`` of given trips.
-    ``tw_improve``: the trips built here under the windows are improved (routing/tw_improve.py)."""
+    ``tw_improve``: the trips built here under the windows are improved (routing/tw_improve.py).
+    ``pd``: the request's ``pickup_from`` per point (routing/shipments.py; it comes with ``tw``): the
+    trips hold pickup -> delivery pairs, ``tw_improve`` is ignored as well and the response also
+    carries ``shipments``."""
     all_points = [source] + list(destinations)
+    demand = [0.0] + [_float(p.get("payload", 0), 0.0) for p in destinations]
     if tw is not None and tw_result is None:
         # (trips that come without their schedule were not planned under the windows)
+        needs = NEEDS_MATRIX_TIMES if pd is None else PD_NEEDS_MATRIX_TIMES
         if not hasattr(provider, "time_matrix"):
-            return {"error": NEEDS_MATRIX_TIMES}
+            return {"error": needs}
         try:
             sec, d = provider.time_matrix(all_points, profile, **_ctx_kw(ctx))
         except ProviderError as e:
-            return {"error": str(e)}
-        demand = [0.0] + [_float(p.get("payload", 0), 0.0) for p in destinations]
+            return {"error": needs if str(e) == NEEDS_MATRIX_TIMES else str(e)}
         try:
-            trips, schedule, tstats = tw_trips(d, sec, demand, _float(driver.get("vehicle_capacity", 9e12), 9e12),
-                                               _float(driver.get("maximum_distance", 9e12), 9e12), *tw)
+            plan = tw_trips if pd is None else pd_trips
+            trips, schedule, tstats = plan(d, sec, demand, _float(driver.get("vehicle_capacity", 9e12), 9e12),
+                                           _float(driver.get("maximum_distance", 9e12), 9e12), *tw,
+                                           *(() if pd is None else (pd,)))
         except InfeasibleStops as e:
             return {"error": str(e)}
-        if tw_improve:
+        if tw_improve and pd is None:
             trips, schedule, search = tw_improve_trips(
                 d, sec, trips, demand, _float(driver.get("vehicle_capacity", 9e12), 9e12),
                 _float(driver.get("maximum_distance", 9e12), 9e12), *tw)
@@ -152,7 +163,11 @@ def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, A
         feature = assemble_trips(provider, all_points, trips, profile, source, destinations, ctx)
         if "error" not in feature and tw_result is not None:
             p = feature["properties"]
-            p["schedule"], p["time_windows"] = schedule_properties(tw_result[0], tw_result[1], tw[1])
+            if pd is None:
+                p["schedule"], p["time_windows"] = schedule_properties(tw_result[0], tw_result[1], tw[1])
+            else:
+                p["schedule"], p["time_windows"], p["shipments"] = shipment_properties(
+                    tw_result[0], tw_result[1], tw[1], demand, pd)
         return feature
     if trips is None:
         try:
@@ -161,7 +176,6 @@ def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, A
             return {"error": str(e)}
         cap = _float(driver.get("vehicle_capacity", 9e12), 9e12)
         max_dist = _float(driver.get("maximum_distance", 9e12), 9e12)
-        demand = [0.0] + [_float(p.get("payload", 0), 0.0) for p in destinations]
         try:
             dm = np.asarray(d, dtype=np.float64)
             trips = greedy_trips(dm.tolist(), demand, cap, max_dist)
@@ -233,16 +247,18 @@ def _optimize(input_data, provider, engine, trips, ctx, improvement, driver, veh
         p["destinations"] = [destinations[0]]
         _annotate(feature, driver, vehicle_type, engine)
         return feature
-    tw = None
-    if wants_time_windows(input_data):
+    tw = pd = None
+    ship = wants_shipments(input_data)
+    if ship or wants_time_windows(input_data):
         try:
             tw = parse_time_windows(input_data)
+            pd = parse_shipments(input_data) if ship else None
         except ValueError as e:
             return {"error": str(e)}
     feature = multi_stop(provider, source, destinations, profile, driver, trips, ctx,
                          improve=wants_improve(input_data), improvement=improvement,
                          exchange=wants_exchange(input_data), tw=tw, tw_result=tw_result,
-                         tw_improve=wants_tw_improve(input_data))
+                         tw_improve=wants_tw_improve(input_data), pd=pd)
     if "error" in feature:
         return feature
     _annotate(feature, driver, vehicle_type, engine)
@@ -288,13 +304,17 @@ def optimize_many(requests: Sequence[Dict[str, Any]], provider, engine: str = "b
 
 
 def _tw_or_none(request):
-    if not wants_time_windows(request):
+    """``(open_q, close_q, sv_q)`` of a time-window request, ``(open_q, close_q, sv_q, pickup_from)``
+    of a shipment request (routing/shipments.py), None for any other and for a malformed one."""
+    ship = wants_shipments(request)
+    if not (ship or wants_time_windows(request)):
         return None
     try:
-        return parse_time_windows(request)
+        tw = parse_time_windows(request)
+        return tw + (parse_shipments(request),) if ship else tw
     except ValueError:
         return None
 
 
 def _tw_malformed(request) -> bool:
-    return wants_time_windows(request) and _tw_or_none(request) is None
+    return (wants_time_windows(request) or wants_shipments(request)) and _tw_or_none(request) is None

@@ -210,7 +210,8 @@ class RouteBatcher:
             mats = prov.router(device).matrices([nodes[k].tolist() for k in multi], key)
             nm = max(len(pts[k]) for k in multi)
             D = np.zeros((len(multi), nm, nm))
-            # time-window requests (routing/timewindows.py) are planned on the seconds as well
+            # time-window and shipment requests (routing/timewindows.py, routing/shipments.py: an
+            # entry of four) are planned on the seconds as well
             tw = [_tw_or_none(payloads[k]) for k in multi]
             T = np.zeros((len(multi), nm, nm)) if any(v is not None for v in tw) else None
             for i, (k, (sec, met)) in enumerate(zip(multi, mats)):
@@ -301,8 +302,8 @@ class RouteBatcher:
                     plan(k, trips.get(k), view, ctxs[k], stats.get(k)) for k in range(len(payloads))]
         multi = [k for k, r in enumerate(payloads) if _valid_points(r) and len(r["destination_points"]) > 1]
         if multi and name in ("haversine", "graph"):
-            # the haversine flush plans time-window requests too; the A* engine has no seconds
-            # matrix, so there optimize_route answers them with its error
+            # the haversine flush plans time-window and shipment requests too; the A* engine has no
+            # seconds matrix, so there optimize_route answers them with its error
             tw = [_tw_or_none(payloads[k]) if name == "haversine" else None for k in multi]
             kw = ({"time_windows": tw, "tw_improve": [wants_tw_improve(payloads[k]) for k in multi]}
                   if any(v is not None for v in tw) else {})
