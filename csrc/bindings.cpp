@@ -679,6 +679,44 @@ torch::Tensor route_tw_improve(torch::Tensor D, torch::Tensor T, torch::Tensor n
   return stats;
 }
 
+// K6g on K6f's own outputs: visit / trip_of / ntrips / arrival / start are rewritten in place for
+// rows with flag != 0 and status == 0 (routing/shipment_improve.py).  Returns stats i64 [R,8] =
+// moves, pair_moves, rejected, trips_before, trips_after, len_before_q, len_after_q, waiting_q (0
+// for rows left alone).
+torch::Tensor route_pd_improve(torch::Tensor D, torch::Tensor T, torch::Tensor npts, torch::Tensor demand,
+                               torch::Tensor cap, torch::Tensor maxd, torch::Tensor open, torch::Tensor close,
+                               torch::Tensor service, torch::Tensor pickup_from, torch::Tensor visit,
+                               torch::Tensor trip_of, torch::Tensor ntrips, torch::Tensor status,
+                               torch::Tensor arrival, torch::Tensor start, torch::Tensor flag) {
+  for (auto* t : {&D, &T, &npts, &demand, &cap, &maxd, &open, &close, &service, &pickup_from, &visit, &trip_of,
+                  &ntrips, &status, &arrival, &start, &flag})
+    check_dev(*t, "route tensor");
+  check_route_D(D, &T);
+  const int R = (int)D.size(0), NM = (int)D.size(1);
+  TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
+  check_route_vec(npts, torch::kInt32, R, "npts");
+  check_route_rows({&demand}, torch::kFloat64, R, NM, "demand");
+  check_route_vec(cap, torch::kFloat64, R, "cap");
+  check_route_vec(maxd, torch::kFloat64, R, "maxd");
+  check_route_rows({&open, &close, &service, &arrival, &start}, torch::kInt64, R, NM,
+                   "open, close, service, arrival and start", " (milliseconds)");
+  check_route_rows({&pickup_from, &visit, &trip_of}, torch::kInt32, R, NM, "pickup_from, visit and trip_of");
+  check_route_vec(ntrips, torch::kInt32, R, "ntrips");
+  check_route_vec(status, torch::kInt32, R, "status");
+  check_route_vec(flag, torch::kUInt8, R, "flag");
+  const c10::DeviceGuard guard(D.device());
+  auto stats = torch::zeros({R, 8}, D.options().dtype(torch::kInt64));
+  RT_CHECK_HIP(rt::launch_pd_improve(
+      D.data_ptr<double>(), T.data_ptr<double>(), npts.data_ptr<int>(), demand.data_ptr<double>(),
+      cap.data_ptr<double>(), maxd.data_ptr<double>(), (const long long*)open.data_ptr<int64_t>(),
+      (const long long*)close.data_ptr<int64_t>(), (const long long*)service.data_ptr<int64_t>(),
+      pickup_from.data_ptr<int>(), flag.data_ptr<uint8_t>(), R, NM, visit.data_ptr<int>(),
+      trip_of.data_ptr<int>(), ntrips.data_ptr<int>(), status.data_ptr<int>(),
+      (long long*)arrival.data_ptr<int64_t>(), (long long*)start.data_ptr<int64_t>(),
+      (long long*)stats.data_ptr<int64_t>(), cur_stream(D)));
+  return stats;
+}
+
 // K10 candidates: (cand i32 [P,k], cand_d2 i64 [P,k], n_cand i32 [P]) of the fixes (py, px) on the
 // graph's bucket grid (routing/mapmatch.py build_grid).
 std::vector<torch::Tensor> mm_candidates(torch::Tensor start, torch::Tensor items, torch::Tensor nqy,
@@ -1756,6 +1794,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("D"), py::arg("T"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"),
         py::arg("open"), py::arg("close"), py::arg("service"), py::arg("visit"), py::arg("trip_of"),
         py::arg("ntrips"), py::arg("status"), py::arg("arrival"), py::arg("start"), py::arg("flag"));
+  m.def("route_pd_improve", &route_pd_improve,
+        "K6g: unit relocate on K6f's outputs (rewritten in place); returns stats [R,8]",
+        py::arg("D"), py::arg("T"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"),
+        py::arg("open"), py::arg("close"), py::arg("service"), py::arg("pickup_from"), py::arg("visit"),
+        py::arg("trip_of"), py::arg("ntrips"), py::arg("status"), py::arg("arrival"), py::arg("start"),
+        py::arg("flag"));
   m.def("route_exchange_trips", &route_exchange_trips,
         "K6c: inter-trip relocate / swap on K6's outputs (visit, trip_of, ntrips rewritten in place)",
         py::arg("D"), py::arg("npts"), py::arg("demand"), py::arg("cap"), py::arg("maxd"), py::arg("visit"),

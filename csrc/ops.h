@@ -265,6 +265,19 @@ hipError_t launch_tw_improve(const double* D, const double* T, const int* npts, 
                              int R, int NM, int* visit, int* trip_of, int* ntrips, const int* status,
                              long long* arrival, long long* start, long long* stats, hipStream_t stream);
 
+// ---- K6g unit relocate on K6f's outputs : route_pd_improve.hip ----
+// visit, trip_of, ntrips, arrival and start are rewritten in place for rows with flag != 0 and
+// status == 0 (routing/shipment_improve.py; still grouped by trip, trip indices compacted) and their
+// stats [R, 8] = moves, pair_moves, rejected, trips_before, trips_after, len_before_q, len_after_q,
+// waiting_q are written; every other row and its stats are not touched.  Inputs as launch_pd_trips
+// takes them.
+hipError_t launch_pd_improve(const double* D, const double* T, const int* npts, const double* demand,
+                             const double* cap, const double* maxd, const long long* open,
+                             const long long* close, const long long* service, const int* pickup_from,
+                             const unsigned char* flag, int R, int NM, int* visit, int* trip_of, int* ntrips,
+                             const int* status, long long* arrival, long long* start, long long* stats,
+                             hipStream_t stream);
+
 // ---- K6c inter-trip relocate / swap on K6's outputs : route_exchange.hip ----
 // visit, trip_of and ntrips are rewritten in place for rows with flag != 0 and status == 0 (still
 // grouped by trip, trip indices compacted); the six statistics are written for every row (0 for

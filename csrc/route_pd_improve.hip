@@ -1,0 +1,685 @@
+// K6g: unit-relocate local search on the trips K6f built for a shipment row (gfx950), opt-in per
+// request row.  A unit is a plain stop or a pickup -> delivery pair; a move takes one out of its trip
+// and puts it into another trip (type 0) or back into its own (type 1).
+//
+// The definition (K6f's fixed point, kinds, mates and load profile; integer-feasible trips; the two
+// move types with K6f's (i, j) position convention; best-improvement selection with the
+// (type, A, x, B, i, j) tie rule; the f64 acceptance walks; the move cap and the skip conditions) and
+// the fast tests evaluated here are in routest_amd/routing/shipment_improve.py; the host C++ is
+// rtr::pd_improve_trips (runtime/route_core.h).  All three are compared with ==: every quantity the
+// search orders by is an int64 sum, so the schedule below cannot change it.
+//
+// One TEAM of threads per request row (teams, tiers and the barrier discipline: route_team.h).
+//
+// The LDS is K6e's image (both quantized matrices as int32, gathered once; open / close / service /
+// demand; route_team.h's flat order in two copies; dep[] and z[] per flat position; Lq per trip)
+// without K6e's swap terms, plus load[] / pm[] per flat position, the plain load and the soundness
+// of every trip, kind / mate per stop and the flat position of every stop.  Per move:
+//   0. one lane per trip walks dep, load and its running maximum pm forwards (with the trip's length
+//      and whether it is sound: legs usable, in time, within cap_q) and z backwards;
+//   1. one lane per unit walks A', its trip without it: the removal term rem = Lq[A] - length(A') and
+//      whether A' is integer-feasible (a seconds matrix need not obey the triangle inequality);
+//   2. the candidate scan: a lane owns an insertion position of the flat order (one in front of
+//      every stop, one closing every trip) and strides over the units, once per move type (the two
+//      types keep different values per position in registers; one pass spilled).  A position of
+//      another trip prices a type-0 move with K6f's candidate code, the walk over j in registers
+//      included.  A position of the unit's own trip is a position of A' (the positions in front of
+//      the unit's own stops repeat the next one and are skipped): the gain is O(1) and the new order
+//      is walked only for a candidate that would replace the lane's best, from the last unchanged
+//      position (old dep / load) to the first failure or the first stop behind every change, where
+//      the old z decides.  No barrier and no cross-lane operation inside.  The lane keeps (max gain, then min move code), six 8-bit fields
+//      below the type;
+//   3. the team reduces; everyone writes the moved order into the second copy, a position a thread;
+//   4. acceptance as K6f measures it: the touched trips' f64 legs and demands are staged into LDS in
+//      parallel and four lanes, one per walk, add them in order (the only place where float
+//      association matters); accepted: the copies change roles; rejected: the search ends.
+// At the end the non-empty trips are compacted as in K6e.
+#include "ops.h"
+#include "route_team.h"
+
+namespace rt {
+
+namespace {
+
+using namespace team;
+
+constexpr int kPlain = 0, kPickup = 1, kDelivery = 2;
+
+// LDS of one team (offsets in bytes), for a stop capacity of kc; [2]: two arrays of stride v8 / v4
+struct PdImproveLds {
+  size_t Q = 0, T = 0, open = 0, close = 0, sv = 0, qd = 0, dep = 0, z = 0, load = 0, pm = 0, Lq = 0, ld0 = 0,
+         rem = 0, dv = 0, dm = 0, ord = 0, tof = 0, tst = 0, cnt = 0, pos = 0, kind = 0, mate = 0, uw = 0, snd = 0,
+         rank = 0, bnd = 0, redg = 0, redc = 0, misc = 0, bytes = 0;
+  int v8 = 0, v4 = 0;
+  __host__ __device__ constexpr explicit PdImproveLds(int kc) {
+    LdsCarve c;
+    Q = c.take(4, (size_t)(kc + 1) * matrix_stride(kc));
+    T = c.take(4, (size_t)(kc + 1) * matrix_stride(kc));
+    open = c.take(8, kc + 4);
+    close = c.take(8, kc + 4);
+    sv = c.take(8, kc + 4);
+    qd = c.take(8, kc + 4);
+    dep = c.take(8, kc + 4);     // per flat position: the departure of its stop
+    z = c.take(8, kc + 4);       // per flat position: the latest start of its stop
+    load = c.take(8, kc + 4);    // per flat position: the load on leaving its stop
+    pm = c.take(8, kc + 4);      // per flat position: the largest load of its trip up to here
+    Lq = c.take(8, kc + 4);      // per trip
+    ld0 = c.take(8, kc + 4);     // per trip: the load on leaving the depot
+    rem = c.take(8, kc + 4);     // per flat position of a unit: Lq[A] - length(A')
+    dv = c.take(8, kc + 4, 2);   // a touched trip's legs
+    dm = c.take(8, kc + 4, 2);   // ... and what its stops add to or take from the load
+    ord = c.take(4, kc + 4, 2);  // the order and its moved copy
+    tof = c.take(4, kc + 4, 2);
+    tst = c.take(4, kc + 4, 2);
+    cnt = c.take(4, kc + 4, 2);
+    pos = c.take(4, kc + 4, 2);  // per stop: its flat position
+    kind = c.take(4, kc + 4);
+    mate = c.take(4, kc + 4);
+    uw = c.take(4, kc + 4);      // x | y of the delivery << 8 | A << 16 | A' feasible << 24 | pair << 25 | unit << 26
+    snd = c.take(4, kc + 4);     // per trip: sound
+    rank = c.take(4, kc + 4);
+    bnd = c.take(4, kc + 4);
+    redg = c.take(8, 16);
+    redc = c.take(8, 16);
+    misc = c.take(4, 8);         // [0..3]: the four walks' verdicts
+    bytes = c.bytes;
+    v8 = (int)(align16((size_t)(kc + 4) * 8) / 8);
+    v4 = (int)(align16((size_t)(kc + 4) * 4) / 4);
+  }
+};
+static_assert(PdImproveLds(32).bytes == 15648 && PdImproveLds(128).bytes == 157728, "the layout is fixed");
+
+// what the per-lane walks read: the team's LDS arrays of the current order
+struct PdView {
+  const int *sQ, *sT;
+  const long long *open, *close, *sv, *qd;
+  const int *kind, *mate, *ord;
+  int S;
+  long long cap_q;
+};
+
+// One lane: the trip at flat positions fb .. fb + kA - 1 without the stops at its positions x and yv
+// (yv == 0: none) and, when u > 0, with u behind position i and v (> 0) behind position j of what is
+// left.  True when every leg is usable, every stop starts in time and the load stays within cap_q.
+// The walk starts behind position y0 of the trip, in front of which nothing changes (y0 < x), with
+// the departure clock and the load ld on leaving it (y0 == 0: the depot, clock 0, the depot load).
+// z == nullptr: the whole rest is walked and len is the millimetre length from y0 on (unusable legs
+// as INT_MAX).  z: the latest starts of the trip as it stands, which must be sound: the walk ends at
+// the first failure, and at the first stop behind every change, where the old z decides for the
+// unchanged rest (its loads and legs are the old ones); len is then not meaningful.
+__device__ __forceinline__ bool walk_without(const PdView& w, int fb, int kA, int x, int yv, int u, int v, int i,
+                                             int j, int y0, long long clock, long long ld, const long long* z,
+                                             long long& len) {
+  bool ok = ld <= w.cap_q;
+  long long L = 0;
+  int prev = y0 == 0 ? 0 : w.ord[fb + y0 - 1], at = y0;
+  const int last = v > 0 ? j : i;  // the position of A' behind which the last stop goes in
+  auto step = [&](int s) {
+    const int ql = w.sQ[prev * w.S + s], tl = w.sT[prev * w.S + s];
+    L += ql;
+    const long long st = max64(clock + tl, w.open[s]);
+    ok = ok && ql != kUnusable && tl != kUnusable && st <= w.close[s];
+    clock = st + w.sv[s];
+    ld += w.kind[s] == kPickup ? w.qd[w.mate[s]] : -w.qd[s];
+    ok = ok && ld <= w.cap_q;
+    prev = s;
+  };
+  if (u > 0 && i == y0) {
+    step(u);
+    if (v > 0 && j == y0) step(v);
+  }
+  for (int y = y0 + 1; y <= kA; ++y) {  // per-lane bounds: no barrier, no cross-lane operation
+    if (y == x || y == yv) continue;
+    ++at;
+    const int s = w.ord[fb + y - 1];
+    if (z != nullptr && y > x && y > yv && at > last) {  // behind every change: the old z decides
+      const int ql = w.sQ[prev * w.S + s], tl = w.sT[prev * w.S + s];
+      len = 0;
+      return ok && ql != kUnusable && tl != kUnusable && max64(clock + tl, w.open[s]) <= z[fb + y - 1];
+    }
+    step(s);
+    if (u > 0 && at == i) step(u);
+    if (v > 0 && at == j) step(v);
+    if (z != nullptr && !ok) break;
+  }
+  if (prev != 0) {
+    const int ql = w.sQ[prev * w.S], tl = w.sT[prev * w.S];
+    L += ql;
+    ok = ok && ql != kUnusable && tl != kUnusable;
+  }
+  len = L;
+  return ok;
+}
+
+__device__ __forceinline__ long long pd_move_code(int type, int A, int x, int B, int i, int j) {
+  return ((long long)type << 40) | ((long long)A << 32) | ((long long)x << 24) | ((long long)B << 16) |
+         ((long long)i << 8) | j;
+}
+
+// KC: stop capacity of the LDS carve (the launch sizes the dynamic region for it).  It must stay the
+// first parameter: launch_two_tiers passes it there, in front of the launch's own arguments.
+template <int TEAM>
+__global__ __launch_bounds__(Team<TEAM>::BLOCK) void pd_improve_kernel(
+    int KC, const double* __restrict__ D, const double* __restrict__ T, const int* __restrict__ npts,
+    const double* __restrict__ demand, const double* __restrict__ cap, const double* __restrict__ maxd,
+    const long long* __restrict__ open, const long long* __restrict__ close,
+    const long long* __restrict__ service, const int* __restrict__ pickup_from,
+    const unsigned char* __restrict__ flag, int R, int NM, int* __restrict__ visit, int* __restrict__ trip_of,
+    int* __restrict__ ntrips, const int* __restrict__ status, long long* __restrict__ arrival,
+    long long* __restrict__ start, long long* __restrict__ stats) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  using Tm = Team<TEAM>;
+  const Row rw = Tm::row(npts, R, NM);
+  if (!rw.mine) return;
+  const int tid = rw.tid, r = rw.r, n = rw.n, ns = rw.ns;
+  if (flag[r] == 0 || status[r] != 0) return;  // not asked for, or not planned: nothing is touched
+  if (ns == 0 || ns > kMaxStops || ns > KC) return;
+
+  const PdImproveLds L(KC);
+  unsigned char* base = smem + (size_t)rw.team * L.bytes;
+  const int S = matrix_stride(KC), V4 = L.v4, V8 = L.v8;
+  int* sQ = (int*)(base + L.Q);
+  int* sT = (int*)(base + L.T);
+  long long* s_open = (long long*)(base + L.open);
+  long long* s_close = (long long*)(base + L.close);
+  long long* s_sv = (long long*)(base + L.sv);
+  long long* s_qd = (long long*)(base + L.qd);
+  long long* s_dep = (long long*)(base + L.dep);
+  long long* s_z = (long long*)(base + L.z);
+  long long* s_load = (long long*)(base + L.load);
+  long long* s_pm = (long long*)(base + L.pm);
+  long long* s_Lq = (long long*)(base + L.Lq);
+  long long* s_ld0 = (long long*)(base + L.ld0);
+  long long* s_rem = (long long*)(base + L.rem);
+  double* s_dv = (double*)(base + L.dv);
+  double* s_dm = (double*)(base + L.dm);
+  const FlatOrder flat = {(int*)(base + L.ord), (int*)(base + L.tof), (int*)(base + L.tst),
+                          (int*)(base + L.cnt)};
+  int* s_pos = (int*)(base + L.pos);
+  int* s_kind = (int*)(base + L.kind);
+  int* s_mate = (int*)(base + L.mate);
+  unsigned* s_uw = (unsigned*)(base + L.uw);
+  int* s_snd = (int*)(base + L.snd);
+  int* s_rank = (int*)(base + L.rank);
+  int* s_bnd = (int*)(base + L.bnd);
+  long long* s_redg = (long long*)(base + L.redg);
+  long long* s_redc = (long long*)(base + L.redc);
+  int* s_misc = (int*)(base + L.misc);
+
+  const double* d = D + (size_t)r * NM * NM;
+  const double* t = T + (size_t)r * NM * NM;
+  const double* dem = demand + (size_t)r * NM;
+  const long long* op = open + (size_t)r * NM;
+  const long long* cl = close + (size_t)r * NM;
+  const long long* sv = service + (size_t)r * NM;
+  const int* pf = pickup_from + (size_t)r * NM;
+  int* vrow = visit + (size_t)r * NM;
+  int* trow = trip_of + (size_t)r * NM;
+  long long* arow = arrival + (size_t)r * NM;
+  long long* strow = start + (size_t)r * NM;
+  long long* srow = stats + (size_t)r * 8;
+  const double MD = maxd[r], CAP = cap[r];
+  const long long cap_q = quantize_limit(CAP), max_q = quantize_limit(MD);
+
+  // ---- the row as K6f left it, from global memory: its trips, its waiting time, its validity
+  long long groups = 0, wait0 = 0, badv = 0;
+  for (int p = tid; p < ns; p += TEAM) {
+    const int v = vrow[p];
+    badv += (v < 1 || v >= n) ? 1 : 0;
+    groups += (p == 0 || trow[p] != trow[p - 1]) ? 1 : 0;
+    wait0 += strow[p] - arow[p];
+  }
+  const int m = (int)Tm::sum(groups, s_redg, tid);
+  wait0 = Tm::sum(wait0, s_redg, tid);
+  if (Tm::sum(badv, s_redg, tid) != 0) return;  // not K6f's output: leave the row alone
+
+  // ---- gather: both quantized matrices, the per-stop vectors, kinds and mates, the order
+  for (int c = tid; c < n * n; c += TEAM) {
+    const int a = c / n, b = c - a * n;
+    sQ[a * S + b] = quantize_entry(d[(size_t)a * NM + b]);
+    sT[a * S + b] = quantize_entry(t[(size_t)a * NM + b]);
+  }
+  for (int s = tid; s < n; s += TEAM) {
+    s_open[s] = s == 0 ? 0 : op[s];
+    s_close[s] = s == 0 ? kUnbounded : cl[s];
+    s_sv[s] = s == 0 ? 0 : sv[s];
+    s_qd[s] = s == 0 ? 0 : quantize_mm(dem[s]);
+    const int p = s == 0 ? -1 : pf[s];
+    const bool named = p >= 1 && p <= ns && p != s;
+    s_kind[s] = named ? kDelivery : kPlain;
+    s_mate[s] = named ? p : 0;
+    s_pos[s] = -1;
+  }
+  flat_build<TEAM>(flat, s_bnd, vrow, trow, ns, tid);  // its first barrier covers the writes above
+  // the pickups learn their deliveries (status 0: K6f found pickup_from well formed) and every stop
+  // its flat position; only kind / mate of stops that are no delivery are written here
+  for (int v = 1 + tid; v <= ns; v += TEAM)
+    if (s_kind[v] == kDelivery) {
+      const int p = s_mate[v];
+      if (s_kind[p] != kDelivery) {
+        s_mate[p] = v;
+        s_kind[p] = kPickup;
+      }
+    }
+  for (int p = tid; p < ns; p += TEAM) s_pos[flat.ord[p]] = p;
+  Tm::sync();
+  // every stop once, a pair in one trip with its pickup first: else the row is not K6f's output
+  long long bad = 0, bigdem = 0;
+  for (int s = 1 + tid; s <= ns; s += TEAM) {
+    const int p = s_pos[s], kd = s_kind[s];
+    bool ok = p >= 0;
+    if (ok && kd == kDelivery) {
+      const int u = s_mate[s], pu = s_pos[u];
+      ok = s_kind[u] == kPickup && s_mate[u] == s && pu >= 0 && pu < p && flat.tof[pu] == flat.tof[p];
+    }
+    bad += ok ? 0 : 1;
+    bigdem += (kd != kPickup && s_qd[s] == kBig) ? 1 : 0;
+  }
+  if (Tm::sum(bad, s_redg, tid) != 0) return;
+  const long long part = flat_trip_sums<TEAM>(flat, m, sQ, S, s_qd, s_Lq, s_rem, tid);  // s_rem: scratch
+  const long long before = Tm::sum(part, s_redg, tid);
+  bigdem = Tm::sum(bigdem, s_redg, tid);
+  if (bigdem != 0 || cap_q < 0 || max_q < 0) {  // the stage is skipped
+    if (tid == 0) {
+      srow[0] = srow[1] = srow[2] = 0;
+      srow[3] = srow[4] = m;
+      srow[5] = srow[6] = before;
+      srow[7] = wait0;
+    }
+    return;
+  }
+
+  // ---- best-improvement search
+  const int ncols = ns + m;  // insertion positions: one in front of every stop, one closing every trip
+  const Lanes ln = Tm::split(ncols, tid);  // ncols >= 2
+  const int CW = ln.CW, col0 = ln.col0, row0 = ln.row0, rstep = ln.rstep;
+  const int limit = 4 * ns;
+  int cur = 0, moves = 0, pair_moves = 0, rejected = 0;
+  while (moves < limit) {
+    Tm::sync();
+    const FlatOrder co = flat.copy(cur, V4);
+    const int *ord = co.ord, *tof = co.tof, *tst = co.tst, *cnt = co.cnt;
+    const int* pos = s_pos + cur * V4;
+    const PdView vw = {sQ, sT, s_open, s_close, s_sv, s_qd, s_kind, s_mate, ord, S, cap_q};
+    // 0. per trip: dep, load and pm forwards, z backwards, its length and whether it is sound
+    for (int x = tid; x < m; x += TEAM) {
+      const int st = tst[x], c = cnt[x];
+      long long len = 0, ld = 0;
+      bool ok = true;
+      if (c > 0) {
+        for (int y = 0; y < c; ++y) {
+          const int b = ord[st + y];
+          ld += s_kind[b] == kPlain ? s_qd[b] : 0;
+        }
+        s_ld0[x] = ld;
+        ok = ld <= cap_q;
+        long long dp = 0, top = ld;
+        int a = 0;
+        for (int y = 0; y < c; ++y) {
+          const int b = ord[st + y];
+          const int ql = sQ[a * S + b], tl = sT[a * S + b];
+          len += ql;
+          const long long stt = max64(dp + tl, s_open[b]);
+          ok = ok && ql != kUnusable && tl != kUnusable && stt <= s_close[b];
+          dp = stt + s_sv[b];
+          ld += s_kind[b] == kPickup ? s_qd[s_mate[b]] : -s_qd[b];
+          top = ld > top ? ld : top;
+          s_dep[st + y] = dp;
+          s_load[st + y] = ld;
+          s_pm[st + y] = top;
+          a = b;
+        }
+        len += sQ[a * S];
+        ok = ok && sQ[a * S] != kUnusable && sT[a * S] != kUnusable && top <= cap_q;
+        long long zz = s_close[a];
+        s_z[st + c - 1] = zz;
+        for (int y = c - 2; y >= 0; --y) {
+          const int b = ord[st + y];
+          const long long v = zz - sT[b * S + a] - s_sv[b];
+          zz = s_close[b] < v ? s_close[b] : v;
+          s_z[st + y] = zz;
+          a = b;
+        }
+      }
+      s_Lq[x] = len;
+      s_snd[x] = ok ? 1 : 0;
+    }
+    Tm::sync();
+    // 1. per unit: the removal term and whether its trip may lose it
+    for (int p = tid; p < ns; p += TEAM) {
+      const int s = ord[p], kd = s_kind[s];
+      unsigned w = 0;
+      if (kd != kDelivery) {
+        const int A = tof[p], fb = tst[A], x = p - fb + 1;
+        const int yv = kd == kPickup ? pos[s_mate[s]] - fb + 1 : 0;
+        long long len;
+        const bool ok = walk_without(vw, fb, cnt[A], x, yv, 0, 0, 0, 0, 0, 0,
+                                     s_ld0[A] - (kd == kPlain ? s_qd[s] : 0), nullptr, len);
+        s_rem[p] = s_Lq[A] - len;
+        w = (unsigned)x | ((unsigned)yv << 8) | ((unsigned)A << 16) | ((ok && len <= max_q) ? 1u << 24 : 0u) |
+            (kd == kPickup ? 1u << 25 : 0u) | (1u << 26);
+      }
+      s_uw[p] = w;
+    }
+    Tm::sync();
+
+    // 2. the candidate scan, in two passes over the lane's insertion positions (the two move types
+    // keep different values per position in registers).  Type 0: K6f's candidates of the units of
+    // other trips behind position i of trip B (a -> b).
+    long long bg = 0, bc = LLONG_MAX;
+    for (int c = col0; c < ncols; c += CW) {
+      const int B = c < ns ? tof[c] : c - ns;
+      const int kB = cnt[B], fb = tst[B];
+      if (kB == 0 || s_snd[B] == 0) continue;  // an emptied trip is never a target, nor is an unsound one
+      const int i = c < ns ? c - fb : kB;
+      const int a = i == 0 ? 0 : ord[fb + i - 1], b = i == kB ? 0 : ord[fb + i];
+      const long long depi = i == 0 ? 0 : s_dep[fb + i - 1], qab = sQ[a * S + b];
+      const long long zn = i < kB ? s_z[fb + i] : 0;
+      const long long ldi = i == 0 ? s_ld0[B] : s_load[fb + i - 1], pmi = i == 0 ? s_ld0[B] : s_pm[fb + i - 1];
+      const long long open_b = s_open[b], sv_b = s_sv[b], LB = s_Lq[B];
+      const int* qa = sQ + a * S;
+      const int* ta = sT + a * S;
+      for (int p = row0; p < ns; p += rstep) {
+        const unsigned w = s_uw[p];
+        const int x = w & 255, A = (w >> 16) & 255;
+        if (!((w >> 24) & 1) || A == B) continue;  // no unit, or one its trip may not lose
+        const bool pair = (w >> 25) & 1;
+        const int u = ord[p];
+        const long long rem = s_rem[p];
+        {
+          const int qau = qa[u], tau = ta[u];
+          if (qau == kUnusable || tau == kUnusable) continue;
+          const long long st = max64(depi + tau, s_open[u]);
+          if (st > s_close[u]) continue;
+          const int qub = sQ[u * S + b], tub = sT[u * S + b];
+          const bool ub = qub != kUnusable && tub != kUnusable;
+          const long long code0 = pd_move_code(0, A, x, B, i, 0);
+          if (!pair) {
+            const long long ins = (long long)qau + qub - qab, g = rem - ins;
+            bool ok = ub && (i == kB || st + s_sv[u] + tub <= zn);
+            ok = ok && pmi + s_qd[u] <= cap_q && LB + ins <= max_q && g > 0;
+            const long long code = code0 | i;
+            if (ok && (g > bg || (g == bg && code < bc))) {
+              bg = g;
+              bc = code;
+            }
+            continue;
+          }
+          const int v = s_mate[u];
+          const long long amt = s_qd[v], open_v = s_open[v], close_v = s_close[v], sv_v = s_sv[v];
+          const long long dpu = st + s_sv[u];  // the departure from the pickup
+          {  // j == i: a -> p -> v -> b
+            const int quv = sQ[u * S + v], tuv = sT[u * S + v], qvb = sQ[v * S + b], tvb = sT[v * S + b];
+            const long long ins = (long long)qau + quv + qvb - qab, g = rem - ins;
+            const long long s2 = max64(dpu + tuv, open_v);
+            bool ok = quv != kUnusable && tuv != kUnusable && qvb != kUnusable && tvb != kUnusable;
+            ok = ok && s2 <= close_v && (i == kB || s2 + sv_v + tvb <= zn);
+            ok = ok && ldi + amt <= cap_q && LB + ins <= max_q && g > 0;
+            const long long code = code0 | i;
+            if (ok && (g > bg || (g == bg && code < bc))) {
+              bg = g;
+              bc = code;
+            }
+          }
+          // j > i: needs the leg p -> b and the stops behind p still in time
+          const long long first = dpu + tub;
+          if (i == kB || !ub || first > zn) continue;
+          const long long ins1 = (long long)qau + qub - qab;
+          long long nd = max64(first, open_b) + sv_b, mx = ldi;
+          int cc = b;                  // t[j]
+          const int* tv = sT + v * S;  // rows of the delivery
+          const int* qv = sQ + v * S;
+          for (int j = i + 1; j <= kB; ++j) {
+            const int e = j == kB ? 0 : ord[fb + j];
+            const long long lj = s_load[fb + j - 1];
+            mx = lj > mx ? lj : mx;
+            const int qcv = sQ[cc * S + v], tcv = sT[cc * S + v], qve = qv[e], tve = tv[e];
+            const long long ins = ins1 + ((long long)qcv + qve - sQ[cc * S + e]), g = rem - ins;
+            const long long s2 = max64(nd + tcv, open_v);
+            const long long zj = j < kB ? s_z[fb + j] : LLONG_MAX;
+            bool ok = qcv != kUnusable && tcv != kUnusable && qve != kUnusable && tve != kUnusable;
+            ok = ok && s2 <= close_v && (j == kB || s2 + sv_v + tve <= zj);
+            ok = ok && mx + amt <= cap_q && LB + ins <= max_q && g > 0;
+            const long long code = code0 | j;
+            const bool take = ok && (g > bg || (g == bg && code < bc));
+            bg = take ? g : bg;
+            bc = take ? code : bc;
+            // the departure from t[j+1] behind the shift (unused behind j == kB)
+            nd = max64(nd + sT[cc * S + e], s_open[e]) + s_sv[e];
+            cc = e;
+          }
+        }
+      }
+    }
+    // Type 1: a position of the unit's own trip is a position of A', the trip without the unit.
+    for (int c = col0; c < ncols; c += CW) {
+      const int B = c < ns ? tof[c] : c - ns;
+      const int kB = cnt[B], fb = tst[B];
+      if (kB < 2) continue;  // A' would be empty
+      const int i = c < ns ? c - fb : kB;
+      const int y = i + 1;  // this position lies in front of the stop at y (kB + 1: the trip's end)
+      const int b = i == kB ? 0 : ord[fb + i];
+      const long long LB = s_Lq[B];
+      const bool sound = s_snd[B] != 0;
+      for (int p = row0; p < ns; p += rstep) {
+        const unsigned w = s_uw[p];
+        const int x = w & 255, yv = (w >> 8) & 255, A = (w >> 16) & 255;
+        if (!((w >> 26) & 1) || A != B) continue;
+        const bool pair = (w >> 25) & 1;
+        const int u = ord[p];
+        const long long rem = s_rem[p];
+        {
+          if (y == x || y == yv) continue;  // in front of the unit's own stop: the next position again
+          if (kB - (pair ? 2 : 1) < 1) continue;
+          const int i1 = i - (x < y ? 1 : 0) - ((pair && yv < y) ? 1 : 0);  // the position in A'
+          int ya = y - 1;
+          while (ya >= 1 && (ya == x || ya == yv)) --ya;
+          const int a1 = ya == 0 ? 0 : ord[fb + ya - 1];  // the stop of A' in front
+          const int qau = sQ[a1 * S + u], qa1b = sQ[a1 * S + b];
+          const long long code0 = pd_move_code(1, A, x, A, i1, 0);
+          const int v = pair ? s_mate[u] : 0;
+          // In a sound trip nothing changes in front of the unit and of this position: the walk
+          // starts there from the old dep / load and ends against the old z.  An unsound trip (a
+          // seed the float tests alone admitted) is walked in full.
+          const int y0 = sound ? (x < y ? x : y) - 1 : 0;
+          // a plain unit's ins and a pair's first bracket
+          const long long ins1 = (long long)qau + sQ[u * S + b] - qa1b;
+          // j == i first; then the delivery behind the stop of A' at yc, ye being the next one
+          int yc = 0, ye = y, j1 = i1;
+          for (;;) {
+            long long ins = ins1;
+            if (j1 > i1) {
+              const int cc = ord[fb + yc - 1], e = ye > kB ? 0 : ord[fb + ye - 1];
+              ins += (long long)sQ[cc * S + v] + sQ[v * S + e] - sQ[cc * S + e];
+            } else if (pair) {
+              ins = (long long)qau + sQ[u * S + v] + sQ[v * S + b] - qa1b;
+            }
+            const long long g = rem - ins;
+            const long long code = code0 | j1;
+            long long len;
+            // the walk only where it can matter, and only over what changes
+            if (g > 0 && (g > bg || (g == bg && code < bc)) && LB - g <= max_q &&
+                walk_without(vw, fb, kB, x, yv, u, v, i1, j1, y0, y0 == 0 ? 0 : s_dep[fb + y0 - 1],
+                             y0 == 0 ? s_ld0[A] : s_load[fb + y0 - 1], sound ? s_z : nullptr, len)) {
+              bg = g;
+              bc = code;
+            }
+            if (!pair || ye > kB) break;
+            yc = ye;
+            ++ye;
+            while (ye <= kB && (ye == x || ye == yv)) ++ye;
+            ++j1;
+          }
+        }
+      }
+    }
+    // 3. (max gain, then min move code) over the team
+    Tm::best(bg, bc, s_redg, s_redc, tid);
+    if (bg <= 0) break;
+
+    // the moved order in the other copy.  In old flat coordinates the unit's stops leave fx and fv
+    // and come back in front of the stops at gi and gj.
+    const int mt = (int)(bc >> 40), mA = (int)(bc >> 32) & 255, mx = (int)(bc >> 24) & 255,
+              mB = (int)(bc >> 16) & 255, mi = (int)(bc >> 8) & 255, mj = (int)bc & 255;
+    const int fa = tst[mA], fx = fa + mx - 1;
+    const int mu = ord[fx];
+    const bool mpair = s_kind[mu] == kPickup;
+    const int mv = mpair ? s_mate[mu] : 0, fv = mpair ? pos[mv] : -1, size = mpair ? 2 : 1;
+    int gi, gj;
+    if (mt == 0) {
+      gi = tst[mB] + mi;
+      gj = tst[mB] + mj;
+    } else {  // the stop number i + 1 of A' as a position of A (behind the last: the trip's end)
+      const int yvv = fv - fa + 1;
+      int yi = mi + 1, yj = mj + 1;
+      yi += yi >= mx ? 1 : 0;
+      yi += (mpair && yi >= yvv) ? 1 : 0;
+      yj += yj >= mx ? 1 : 0;
+      yj += (mpair && yj >= yvv) ? 1 : 0;
+      gi = fa + yi - 1;
+      gj = fa + yj - 1;
+    }
+    const FlatOrder nx = flat.copy(cur ^ 1, V4);
+    int* npos = s_pos + (cur ^ 1) * V4;
+    for (int p = tid; p < ns; p += TEAM) {
+      const int s = ord[p];
+      int np, nt = tof[p];
+      if (p == fx) {
+        np = gi - (fx < gi ? 1 : 0) - ((mpair && fv < gi) ? 1 : 0);
+        nt = mB;
+      } else if (p == fv) {
+        np = gj - (fx < gj ? 1 : 0) - (fv < gj ? 1 : 0) + 1;
+        nt = mB;
+      } else {
+        np = p - (fx < p ? 1 : 0) - ((mpair && fv < p) ? 1 : 0) + (gi <= p ? 1 : 0) + ((mpair && gj <= p) ? 1 : 0);
+      }
+      nx.ord[np] = s;
+      nx.tof[np] = nt;
+      npos[s] = np;
+    }
+    for (int x = tid; x < m; x += TEAM) {
+      const int shift = mt == 0 ? size * ((mB < x ? 1 : 0) - (mA < x ? 1 : 0)) : 0;
+      nx.tst[x] = tst[x] + shift;
+      nx.cnt[x] = cnt[x] + (mt == 0 ? size * ((x == mB ? 1 : 0) - (x == mA ? 1 : 0)) : 0);
+    }
+    Tm::sync();
+    // 4. acceptance as K6f measures it, over the touched non-empty trips: their f64 legs and what
+    // their stops add to or take from the load are staged in parallel, then one lane per walk
+    const int walks = mt == 0 ? 2 : 1;
+    for (int x = 0; x < walks; ++x) {
+      const int tr = x == 0 ? mA : mB;
+      const int st = nx.tst[tr], c = nx.cnt[tr];
+      if (c == 0) continue;
+      for (int e = tid; e <= c; e += TEAM) {
+        const int a = e == 0 ? 0 : nx.ord[st + e - 1];
+        const int b = e == c ? 0 : nx.ord[st + e];
+        s_dv[x * V8 + e] = d[(size_t)a * NM + b];
+        if (e < c) s_dm[x * V8 + e] = dem[s_kind[b] == kPickup ? s_mate[b] : b];
+      }
+    }
+    Tm::sync();
+    if (tid < 4) {
+      const int x = tid >> 1;
+      int ok = 1;
+      if (x < walks) {
+        const int tr = x == 0 ? mA : mB;
+        const int st = nx.tst[tr], c = nx.cnt[tr];
+        const double* wv = s_dv + x * V8;
+        const double* wm = s_dm + x * V8;
+        if (c > 0 && (tid & 1) == 0) {
+          double s = 0.0;
+          for (int p = 0; p < c; ++p) s += wv[p];
+          ok = s + wv[c] <= MD ? 1 : 0;
+        } else if (c > 0) {
+          double bs = 0.0;
+          for (int p = 0; p < c; ++p)
+            if (s_kind[nx.ord[st + p]] == kPlain) bs += wm[p];
+          bool fits = bs <= CAP;
+          double load = bs;
+          for (int p = 0; p < c; ++p) {
+            if (s_kind[nx.ord[st + p]] == kPickup) {
+              load += wm[p];
+              fits = fits && load <= CAP;
+            } else {
+              load -= wm[p];
+            }
+          }
+          ok = fits ? 1 : 0;
+        }
+      }
+      s_misc[tid] = ok;
+    }
+    Tm::sync();
+    if (!(s_misc[0] != 0 && s_misc[1] != 0 && s_misc[2] != 0 && s_misc[3] != 0)) {
+      rejected = 1;  // undone: the first copy stays, the search ends
+      break;
+    }
+    cur ^= 1;
+    ++moves;
+    pair_moves += mpair ? 1 : 0;
+  }
+  Tm::sync();
+
+  // ---- the non-empty trips, compacted in their order, with their schedule
+  const FlatOrder fin = flat.copy(cur, V4);
+  const int *ord = fin.ord, *tof = fin.tof, *tst = fin.tst, *cnt = fin.cnt;
+  // one lane per trip walks its schedule: arrivals into z[], starts into dep[] (no longer needed),
+  // and its length as it stands
+  for (int x = tid; x < m; x += TEAM) {
+    const int st = tst[x], c = cnt[x];
+    long long dp = 0, len = 0;
+    int a = 0;
+    for (int y = 0; y < c; ++y) {
+      const int b = ord[st + y];
+      const long long ar = dp + sT[a * S + b];
+      const long long stt = max64(ar, s_open[b]);
+      len += sQ[a * S + b];
+      s_z[st + y] = ar;
+      s_dep[st + y] = stt;
+      dp = stt + s_sv[b];
+      a = b;
+    }
+    s_Lq[x] = c > 0 ? len + sQ[a * S] : 0;
+  }
+  Tm::sync();
+  if (tid == 0) {
+    long long after;
+    const int k = flat_rank(cnt, s_Lq, m, s_rank, after);
+    ntrips[r] = k;
+    srow[0] = moves;
+    srow[1] = pair_moves;
+    srow[2] = rejected;
+    srow[3] = m;
+    srow[4] = k;
+    srow[5] = before;
+    srow[6] = after;
+  }
+  Tm::sync();
+  long long wait_part = 0;
+  for (int p = tid; p < ns; p += TEAM) {
+    vrow[p] = ord[p];
+    trow[p] = s_rank[tof[p]];
+    arow[p] = s_z[p];
+    strow[p] = s_dep[p];
+    wait_part += s_dep[p] - s_z[p];
+  }
+  const long long waiting = Tm::sum(wait_part, s_redg, tid);
+  if (tid == 0) srow[7] = waiting;
+}
+
+}  // namespace
+
+hipError_t launch_pd_improve(const double* D, const double* T, const int* npts, const double* demand,
+                             const double* cap, const double* maxd, const long long* open,
+                             const long long* close, const long long* service, const int* pickup_from,
+                             const unsigned char* flag, int R, int NM, int* visit, int* trip_of, int* ntrips,
+                             const int* status, long long* arrival, long long* start, long long* stats,
+                             hipStream_t stream) {
+  // both int32 matrices of 128 stops (2 x 66.6 KB) and the per-stop / per-position / per-trip arrays
+  return team::launch_two_tiers<PdImproveLds>(pd_improve_kernel<64>, pd_improve_kernel<team::kLargeTeam>, R, NM,
+                                              stream, D, T, npts, demand, cap, maxd, open, close, service,
+                                              pickup_from, flag, R, NM, visit, trip_of, ntrips, status, arrival,
+                                              start, stats);
+}
+
+}  // namespace rt

@@ -1,7 +1,7 @@
-// What the trip kernels K6b-K6f (route_improve / route_exchange / route_tw / route_tw_improve /
-// route_pd .hip) share, each piece defined once: the fixed-point constants and quantizers, the team
-// of threads with its reductions, the row prologue, the LDS carve, the two-tier launcher and the
-// flat trip order of K6c / K6e.  Only those five files include this header.
+// What the trip kernels K6b-K6g (route_improve / route_exchange / route_tw / route_tw_improve /
+// route_pd / route_pd_improve .hip) share, each piece defined once: the fixed-point constants and
+// quantizers, the team of threads with its reductions, the row prologue, the LDS carve, the two-tier
+// launcher and the flat trip order of K6c / K6e / K6g.  Only those six files include this header.
 //
 // Teams and tiers.  One TEAM of threads works on one request row:
 //   * small tier: rows with at most 32 stops, TEAM = one wavefront, four rows per 256-thread block

@@ -584,6 +584,66 @@ py::tuple tw_improve(py::array_t<double, py::array::c_style | py::array::forceca
   return py::make_tuple(trips, sched, s);
 }
 
+// ------------------------------------------------------------------ unit relocate on shipment trips (shipment_improve.py)
+// (D, T [n1, n1], trips, demand [n1], cap, max_dist, open_q, close_q, sv_q, pickup_from [n1]) ->
+// (trips, schedule, {moves, pair_moves, rejected, trips_before, trips_after, len_before_q,
+// len_after_q, waiting_q})
+py::tuple pd_improve(py::array_t<double, py::array::c_style | py::array::forcecast> D,
+                     py::array_t<double, py::array::c_style | py::array::forcecast> T,
+                     std::vector<std::vector<int>> trips, std::vector<double> demand, double cap, double maxd,
+                     std::vector<long long> open, std::vector<long long> close, std::vector<long long> sv,
+                     std::vector<int> pickup_from) {
+  if (D.ndim() != 2 || D.shape(0) != D.shape(1)) throw std::invalid_argument("D must be square");
+  const int n1 = (int)D.shape(0);
+  if (T.ndim() != 2 || T.shape(0) != n1 || T.shape(1) != n1) throw std::invalid_argument("T must have D's shape");
+  if (n1 < 1) throw std::invalid_argument("D holds at least the depot");
+  if ((int)demand.size() != n1 || (int)open.size() != n1 || (int)close.size() != n1 || (int)sv.size() != n1 ||
+      (int)pickup_from.size() != n1)
+    throw std::invalid_argument("demand, open_q, close_q, sv_q and pickup_from hold one entry per point");
+  std::vector<int> kind, mate;
+  if (!rtr::pd_kinds(pickup_from, n1, kind, mate))
+    throw std::invalid_argument("pickup_from must name another stop that is no delivery and no other delivery's pickup");
+  std::vector<int> at(n1, -1), pos(n1, -1);
+  for (size_t k = 0; k < trips.size(); ++k) {
+    const auto& t = trips[k];
+    if (t.size() < 3 || t.front() != 0 || t.back() != 0)
+      throw std::invalid_argument("a trip starts and ends at the depot and holds a stop");
+    for (size_t p = 1; p + 1 < t.size(); ++p) {
+      if (t[p] < 1 || t[p] >= n1 || at[t[p]] >= 0) throw std::invalid_argument("trips must hold every stop once");
+      at[t[p]] = (int)k;
+      pos[t[p]] = (int)p;
+    }
+  }
+  for (int s = 1; s < n1; ++s) {
+    if (at[s] < 0) throw std::invalid_argument("trips must hold every stop once");
+    if (kind[s] == rtr::kPdPickup && (at[mate[s]] != at[s] || pos[mate[s]] < pos[s]))
+      throw std::invalid_argument("a pair sits in one trip with its pickup first");
+  }
+  const std::vector<double> d(D.data(), D.data() + (size_t)n1 * n1), t(T.data(), T.data() + (size_t)n1 * n1);
+  std::vector<std::vector<long long>> arr, sta;
+  const rtr::PdImproveStats st =
+      rtr::pd_improve_trips(d, t, n1, demand, cap, maxd, open, close, sv, kind, mate, trips, arr, sta);
+  py::list sched;
+  for (size_t k = 0; k < trips.size(); ++k) {
+    py::list one;
+    for (size_t i = 0; i < arr[k].size(); ++i) {
+      const int s = trips[k][i + 1];
+      one.append(py::make_tuple(s, arr[k][i], sta[k][i], sta[k][i] + sv[s]));
+    }
+    sched.append(one);
+  }
+  py::dict s;
+  s["moves"] = st.moves;
+  s["pair_moves"] = st.pair_moves;
+  s["rejected"] = st.rejected;
+  s["trips_before"] = st.trips_before;
+  s["trips_after"] = st.trips_after;
+  s["len_before_q"] = st.len_before_q;
+  s["len_after_q"] = st.len_after_q;
+  s["waiting_q"] = st.waiting_q;
+  return py::make_tuple(trips, sched, s);
+}
+
 PYBIND11_MODULE(_rt, m) {
   m.doc() = "routest_amd CPU native runtime";
   bind_route(m);
@@ -612,6 +672,8 @@ PYBIND11_MODULE(_rt, m) {
         py::arg("open_q"), py::arg("close_q"), py::arg("sv_q"), py::arg("pickup_from"));
   m.def("tw_improve", &tw_improve, py::arg("D"), py::arg("T"), py::arg("trips"), py::arg("demand"), py::arg("cap"),
         py::arg("max_dist"), py::arg("open_q"), py::arg("close_q"), py::arg("sv_q"));
+  m.def("pd_improve", &pd_improve, py::arg("D"), py::arg("T"), py::arg("trips"), py::arg("demand"), py::arg("cap"),
+        py::arg("max_dist"), py::arg("open_q"), py::arg("close_q"), py::arg("sv_q"), py::arg("pickup_from"));
   m.def("astar_batch", &astar_batch, py::arg("indptr"), py::arg("indices"), py::arg("cost"),
         py::arg("lat"), py::arg("lon"), py::arg("src"), py::arg("dst"), py::arg("inv_vmax"),
         py::arg("threads") = 8);

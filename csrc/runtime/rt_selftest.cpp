@@ -1251,6 +1251,183 @@ static void fuzz_pd(std::mt19937_64& rng, int iters) {
   }
 }
 
+// route_core.h pd_improve_trips on pd_trips' output (instances as in fuzz_pd, half as many).  After
+// the search every stop is present exactly once, every pair sits in one trip with its pickup first
+// and every trip re-simulates as feasible (legs and time always; load and length for the trips a
+// move touched: a seed is admitted by the float tests alone).  The applied sequence is replayed from
+// pd_trips' trips by the definition: each move's trips re-simulate as integer-feasible, its gain is
+// positive, and the replay ends in the trips and the length that came out.
+static void fuzz_pd_improve(std::mt19937_64& rng, int iters) {
+  for (int it = 0; it < iters / 400; ++it) {
+    const int n1 = 1 + (int)(rng() % 34);
+    std::vector<double> d((size_t)n1 * n1, 0.0), t((size_t)n1 * n1, 0.0), dem(n1, 0.0);
+    for (int a = 0; a < n1; ++a)
+      for (int b = 0; b < n1; ++b)
+        if (a != b) {
+          d[(size_t)a * n1 + b] = 100.0 + (double)(rng() % 1000000) / 37.0;
+          t[(size_t)a * n1 + b] = 10.0 + (double)(rng() % 100000) / 53.0;
+        }
+    if (rng() % 3 == 0 && n1 > 4) {
+      const double bad[6] = {NAN, INFINITY, -5.0, 2147483.647, 3e9, 1e300};
+      for (int x = 0; x < 6; ++x) {
+        std::vector<double>& m = rng() % 2 ? d : t;
+        const int a = rng() % 8 == 0 ? 0 : 1 + (int)(rng() % (n1 - 1)), b = 1 + (int)(rng() % (n1 - 1));
+        if (a != b) m[(size_t)a * n1 + b] = bad[rng() % 6];
+      }
+    }
+    std::vector<long long> open(n1, 0), close(n1, rtr::kExchangeUnbounded), sv(n1, 0);
+    for (int s = 1; s < n1; ++s) {
+      dem[s] = (double)(1 + rng() % 3);
+      if (rng() % 10 < 4) {
+        open[s] = (long long)(rng() % 20000000);
+        close[s] = open[s] + (long long)(rng() % 3 == 0 ? 0 : rng() % 8000000);
+        if (rng() % 4 == 0) open[s] = 0;
+      }
+      if (rng() % 2) sv[s] = (long long)(rng() % 600000);
+    }
+    std::vector<int> order, pf(n1, -1);
+    for (int s = 1; s < n1; ++s) order.push_back(s);
+    for (size_t x = order.size(); x > 1; --x) std::swap(order[x - 1], order[rng() % x]);
+    for (size_t x = 0; x < order.size() / 4; ++x) pf[order[2 * x + 1]] = order[2 * x];
+    const bool free_run = rng() % 3 == 0;
+    const double cap = free_run ? 9e12 : (rng() % 16 == 0 ? NAN : (double)(3 + rng() % 30));
+    const double maxd = free_run ? 9e12 : (rng() % 16 == 0 ? -1.0 : 60000.0 + (double)(rng() % 400000));
+    std::vector<int> kind, mate;
+    CHECK(rtr::pd_kinds(pf, n1, kind, mate), "pd_kinds refused well-formed pairs");
+    std::vector<std::vector<int>> trips;
+    std::vector<std::vector<long long>> arr, sta;
+    std::vector<int> bad;
+    rtr::TwStats st0;
+    if (!rtr::pd_trips(d, t, n1, dem, cap, maxd, open, close, sv, kind, mate, trips, arr, sta, bad, st0)) continue;
+    const std::vector<std::vector<int>> given = trips;
+    long long cap_q = -1, max_q = -1;
+    if (!rtr::exchange_limit(cap, cap_q)) cap_q = -1;
+    if (!rtr::exchange_limit(maxd, max_q)) max_q = -1;
+    // the definition's tests of one trip, independent of route_core.h's walk
+    auto simulate = [&](const std::vector<int>& tr, long long& len, bool& timed, bool& within) {
+      len = 0;
+      timed = within = true;
+      if (tr.size() < 3) return;
+      long long clock = 0, load = 0;
+      for (size_t p = 1; p + 1 < tr.size(); ++p)
+        if (kind[tr[p]] == rtr::kPdPlain) load += rtr::improve_q(dem[tr[p]]);
+      within = load <= cap_q;
+      for (size_t p = 0; p + 1 < tr.size(); ++p) {
+        const int a = tr[p], b = tr[p + 1];
+        const long long q = rtr::tw_q(d[(size_t)a * n1 + b]), qt = rtr::tw_q(t[(size_t)a * n1 + b]);
+        timed = timed && q < rtr::kImproveBig && qt < rtr::kImproveBig;
+        len += q;
+        if (b == 0) break;
+        const long long s0 = std::max(clock + qt, open[b]);
+        timed = timed && s0 <= close[b];
+        clock = s0 + sv[b];
+        load += kind[b] == rtr::kPdPickup ? rtr::improve_q(dem[mate[b]]) : -rtr::improve_q(dem[b]);
+        within = within && load <= cap_q;
+      }
+      within = within && len <= max_q;
+    };
+    std::vector<rtr::PdMove> applied;
+    const rtr::PdImproveStats st =
+        rtr::pd_improve_trips(d, t, n1, dem, cap, maxd, open, close, sv, kind, mate, trips, arr, sta, &applied);
+    CHECK(st.moves == (long long)applied.size() && st.moves <= 4LL * (n1 - 1), "pd_improve: %lld moves, %zu applied", st.moves,
+          applied.size());
+    CHECK(st.trips_before == (long long)given.size() && st.trips_after == (long long)trips.size(), "pd_improve trip counts");
+    // the replay
+    std::vector<std::vector<int>> cur = given;
+    std::vector<char> touched(given.size(), 0);
+    long long pairs = 0, total = 0;
+    bool replayed = true;
+    for (const rtr::PdMove& mv : applied) {
+      if (mv.A < 0 || mv.A >= (int)cur.size() || mv.B < 0 || mv.B >= (int)cur.size() || mv.x < 1 ||
+          mv.x + 1 >= (int)cur[mv.A].size() || (mv.type == 0) == (mv.A == mv.B)) {
+        replayed = false;
+        break;
+      }
+      const int u = cur[mv.A][mv.x], v = kind[u] == rtr::kPdPickup ? mate[u] : -1;
+      if (kind[u] == rtr::kPdDelivery) { replayed = false; break; }
+      pairs += v >= 0;
+      long long before = 0, after = 0, len;
+      bool timed, within;
+      simulate(cur[mv.A], len, timed, within);
+      before += len;
+      if (mv.type == 0) {
+        simulate(cur[mv.B], len, timed, within);
+        before += len;
+      }
+      std::vector<int> rest;
+      for (size_t p = 0; p < cur[mv.A].size(); ++p)
+        if (p == 0 || p + 1 == cur[mv.A].size() || (cur[mv.A][p] != u && cur[mv.A][p] != v)) rest.push_back(cur[mv.A][p]);
+      std::vector<int> into = mv.type == 0 ? cur[mv.B] : rest;
+      const int k = (int)into.size() - 2;
+      if (k < 1 || mv.i < 0 || mv.i > mv.j || mv.j > k || (v < 0 && mv.i != mv.j)) { replayed = false; break; }
+      if (v >= 0) into.insert(into.begin() + mv.j + 1, v);
+      into.insert(into.begin() + mv.i + 1, u);
+      if (mv.type == 0) cur[mv.A] = rest;
+      cur[mv.B] = into;
+      touched[mv.A] = touched[mv.B] = 1;
+      for (int x : {mv.A, mv.B}) {
+        simulate(cur[x], len, timed, within);
+        CHECK(timed && within, "pd_improve applied a move whose trip %d is not integer-feasible", x);
+        if (x == mv.A || mv.type == 0) after += len;
+        if (mv.type == 1) break;
+      }
+      CHECK(before - after > 0, "pd_improve applied a move of gain %lld", before - after);
+    }
+    CHECK(replayed, "pd_improve reported a move outside the definition's ranges");
+    CHECK(pairs == st.pair_moves, "pd_improve pair moves: %lld / %lld", st.pair_moves, pairs);
+    std::vector<std::vector<int>> kept;
+    std::vector<char> kept_touched;
+    for (size_t x = 0; x < cur.size(); ++x)
+      if (cur[x].size() > 2) {
+        kept.push_back(cur[x]);
+        kept_touched.push_back(touched[x]);
+      }
+    CHECK(replayed && kept == trips, "pd_improve: the replay of the applied moves ends in other trips");
+    // the invariants of what came out
+    std::vector<int> seen(n1, 0), trip_of(n1, -1), pos_of(n1, -1);
+    long long waiting = 0;
+    CHECK(trips.size() == arr.size() && trips.size() == sta.size(), "pd_improve schedule count");
+    for (size_t k = 0; k < trips.size(); ++k) {
+      const std::vector<int>& tr = trips[k];
+      CHECK(tr.size() >= 3 && tr.front() == 0 && tr.back() == 0, "pd_improve broke a trip's ends");
+      CHECK(arr[k].size() + 2 == tr.size() && sta[k].size() + 2 == tr.size(), "pd_improve schedule length");
+      long long len, clock = 0;
+      bool timed, within;
+      simulate(tr, len, timed, within);
+      total += len;
+      CHECK(timed, "pd_improve left a trip that does not re-simulate as feasible");
+      if (kept == trips && kept_touched[k]) CHECK(within, "pd_improve left a touched trip over its load or length");
+      for (size_t p = 1; p + 1 < tr.size() && p <= arr[k].size(); ++p) {
+        const int b = tr[p];
+        if (b < 1 || b >= n1) break;
+        ++seen[b];
+        trip_of[b] = (int)k;
+        pos_of[b] = (int)p;
+        const long long ar = clock + rtr::tw_q(t[(size_t)tr[p - 1] * n1 + b]), s0 = std::max(ar, open[b]);
+        CHECK(arr[k][p - 1] == ar && sta[k][p - 1] == s0, "pd_improve schedule entry");
+        waiting += s0 - ar;
+        clock = s0 + sv[b];
+      }
+      double s = 0.0;
+      const int kk = (int)tr.size() - 2;
+      for (int p = 0; p < kk; ++p) s += d[(size_t)tr[p] * n1 + tr[p + 1]];
+      CHECK(s + d[(size_t)tr[kk] * n1] <= maxd && rtr::pd_load_feasible(dem, kind, mate, tr, cap),
+            "pd_improve kept a trip that fails the float walks");
+    }
+    bool once = true, paired = true;
+    for (int s = 1; s < n1; ++s) {
+      once = once && seen[s] == 1;
+      if (kind[s] == rtr::kPdPickup) paired = paired && trip_of[s] == trip_of[mate[s]] && pos_of[s] < pos_of[mate[s]];
+    }
+    CHECK(once, "pd_improve lost or repeated a stop");
+    CHECK(paired, "pd_improve split a pair or delivered before the pickup");
+    CHECK(total == st.len_after_q && waiting == st.waiting_q && st.len_after_q <= st.len_before_q &&
+              st.len_before_q == st0.len_q,
+          "pd_improve statistics: len %lld -> %lld / %lld, waiting %lld / %lld", st.len_before_q, st.len_after_q, total,
+          st.waiting_q, waiting);
+  }
+}
+
 int main(int argc, char** argv) {
   const int iters = argc > 1 ? std::atoi(argv[1]) : 20000;
   std::mt19937_64 rng(argc > 2 ? std::strtoull(argv[2], nullptr, 10) : 1234);
@@ -1270,6 +1447,7 @@ int main(int argc, char** argv) {
   fuzz_avoid_mask(rng, iters);
   fuzz_tw_improve(rng, iters);
   fuzz_pd(rng, iters);
+  fuzz_pd_improve(rng, iters);
   store_while_reading();
   threaded_pack_format(20000);
   std::printf("rt_selftest: %d iterations, %d failures\n", iters, g_fail);

@@ -14,7 +14,9 @@ instead (on a GPU one launch, K6d, over the flagged rows only); per-request ``tw
 the window-aware local search of :mod:`routing.tw_improve` on those rows (on a GPU one more launch, K6e).
 A ``time_windows`` entry of four, ``pickup_from`` per point behind the windows, makes its row a
 shipment row: pickup -> delivery pairs planned by :mod:`routing.shipments` (on a GPU one launch, K6f,
-over those rows only); such a row is none of K6b's, K6c's, K6d's or K6e's.
+over those rows only); such a row is none of K6b's, K6c's, K6d's or K6e's.  Per-request
+``shipment_improve`` flags add the unit-relocate search of :mod:`routing.shipment_improve` on those
+rows (on a GPU one more launch, K6g).
 Sharding over several GPUs is done by
 :class:`routing.route_batcher.RouteBatcher` (one worker thread per device, no collective).
 """
@@ -30,6 +32,7 @@ from .greedy import InfeasibleStops, greedy_trips
 from .exchange import UNBOUNDED, improve_exchange_trips
 from .improve import improve_trips
 from .providers import haversine_matrix
+from .shipment_improve import STAT_KEYS as PDI_STAT_KEYS, pd_improve_trips
 from .shipments import pd_trips
 from .timewindows import MAX_STOPS as TW_MAX_STOPS, tw_trips
 from .tw_improve import STAT_KEYS as TWI_STAT_KEYS, tw_improve_trips
@@ -147,21 +150,28 @@ def pack_shipments(time_windows: Sequence[Any], nm: int):
     return pf, flags
 
 
-def _pd_device(C, t, D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, pd):
-    """K6f over the shipment rows: K6d's seven outputs, on the host."""
+def _pd_device(C, t, D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, pd, pdi=None):
+    """K6f over the shipment rows: K6d's seven outputs, on the host, and the statistics [R, 8] of
+    K6g over the rows of them that ``pdi`` flags (None: nobody asks)."""
     pf, pdf = pd
-    out = C.route_pd_trips(D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, t(pf, torch.int32),
-                           t(pdf, torch.uint8))
+    pf_t = t(pf, torch.int32)
+    out = C.route_pd_trips(D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, pf_t, t(pdf, torch.uint8))
+    search = None
+    if pdi is not None and (pdi & pdf).any():
+        # K6g rewrites K6f's outputs in place for the asking rows; K6f's own statistics stay
+        search = C.route_pd_improve(D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, pf_t, *out[:6],
+                                    t(pdi & pdf, torch.uint8)).cpu().numpy()
     out = [c.cpu().numpy() for c in out]
     if (out[3][pdf != 0] == 3).any():
         raise ValueError("pickup_from must name another stop that is no delivery and no other delivery's pickup")
-    return out
+    return out, search
 
 
-def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw, twi=None, pd=None):
+def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw, twi=None, pd=None, pdi=None):
     """K6d over the flagged rows: ``{row: trips or InfeasibleStops}``, ``{row: (schedule, stats)}``.
     ``twi``: uint8 flags of the rows whose trips K6e then improves (``stats["search"]``).  ``pd``:
-    ``(pickup_from, flags)`` of :func:`pack_shipments`; those rows are K6f's, not K6d's or K6e's."""
+    ``(pickup_from, flags)`` of :func:`pack_shipments`; those rows are K6f's, not K6d's or K6e's.
+    ``pdi``: uint8 flags of the shipment rows whose trips K6g then improves (``stats["search"]``)."""
     op, cl, sv, twf, speed = tw
     if T is None:
         # one IEEE division per entry, as HaversineProvider.time_matrix does it on the host
@@ -181,9 +191,11 @@ def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw, twi=None, pd=
                                         t(twi & k6d, torch.uint8)).cpu().numpy()
             twi = twi & k6d
         out = [c.cpu().numpy() for c in out]
+    psearch = None
     if pdf.any():
         # K6f's rows beside K6d's (a batch without shipment rows launches nothing more)
-        ship = _pd_device(C, t, D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, pd)
+        ship, psearch = _pd_device(C, t, D, T, npts_t, dem_t, cap_t, maxd_t, op_t, cl_t, sv_t, pd, pdi)
+        pdi = pdi & pdf if psearch is not None else None
         if out is None:
             out = ship
         else:
@@ -209,13 +221,16 @@ def _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw, twi=None, pd=
                           "len_q": int(stats[k, 2]), "waiting_q": int(stats[k, 3])})
         if search is not None and twi[k]:
             sched[k][1]["search"] = {key: int(v) for key, v in zip(TWI_STAT_KEYS, search[k])}
+        if psearch is not None and pdi[k]:
+            sched[k][1]["search"] = {key: int(v) for key, v in zip(PDI_STAT_KEYS, psearch[k])}
     return res, sched
 
 
 def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device,
                          D: Optional[np.ndarray] = None, improve: Optional[Sequence[Any]] = None,
                          exchange: Optional[Sequence[Any]] = None, tw=None, T: Optional[np.ndarray] = None,
-                         tw_improve: Optional[Sequence[Any]] = None, pd=None):
+                         tw_improve: Optional[Sequence[Any]] = None, pd=None,
+                         shipment_improve: Optional[Sequence[Any]] = None):
     # K6 indexes its LDS order / visited arrays by stop number: a request longer than the padded
     # width would write past them, so it is refused here, before anything reaches the device
     nm = int(D.shape[1]) if D is not None else int(np.shape(lat)[1])
@@ -257,7 +272,8 @@ def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device
         twres: List[Any] = [None] * len(n)
         if tw[3].any():
             planned, sched = _tw_device(C, t, D, T, npts, npts_t, dem_t, cap_t, maxd_t, tw,
-                                        _flags(tw_improve, len(n)), pd)
+                                        _flags(tw_improve, len(n)), pd,
+                                        _flags(shipment_improve, len(n)) if pd is not None else None)
             for k, v in planned.items():
                 out[k] = v
                 twres[k] = sched.get(k)
@@ -285,10 +301,12 @@ def batched_trips_device(lat, lon, dem, npts, cap, maxd, circuity: float, device
 def batched_trips_cpu(lat, lon, dem, npts, cap, maxd, circuity: float,
                       D: Optional[np.ndarray] = None, improve: Optional[Sequence[Any]] = None,
                       exchange: Optional[Sequence[Any]] = None, tw=None, T: Optional[np.ndarray] = None,
-                      tw_improve: Optional[Sequence[Any]] = None, pd=None):
+                      tw_improve: Optional[Sequence[Any]] = None, pd=None,
+                      shipment_improve: Optional[Sequence[Any]] = None):
     out: List[TripsOrError] = []
     flags, xflags = _both_flags(improve, exchange, len(npts))
     twi = _flags(tw_improve, len(npts))
+    pdi = _flags(shipment_improve, len(npts))
     stats: List[Optional[Dict[str, int]]] = []
     twres: List[Any] = []
     for k in range(len(npts)):
@@ -310,6 +328,12 @@ def batched_trips_cpu(lat, lon, dem, npts, cap, maxd, circuity: float,
                     # the reference of K6e (routing/tw_improve.py) on the insertion's trips
                     trips, sched, search = tw_improve_trips(d, sec, trips, dem[k, :n].tolist(), float(cap[k]),
                                                             float(maxd[k]), tw[0][k, :n], tw[1][k, :n], tw[2][k, :n])
+                    tst = dict(tst, trips=len(trips), search=search)
+                if pdi is not None and pdi[k] and pd is not None and pd[1][k]:
+                    # the reference of K6g (routing/shipment_improve.py) on the insertion's trips
+                    trips, sched, search = pd_improve_trips(d, sec, trips, dem[k, :n].tolist(), float(cap[k]),
+                                                            float(maxd[k]), tw[0][k, :n], tw[1][k, :n], tw[2][k, :n],
+                                                            pd[0][k, :n].tolist())
                     tst = dict(tst, trips=len(trips), search=search)
                 out.append(trips)
                 twres.append((sched, tst))
@@ -340,7 +364,8 @@ def batched_trips(requests: Sequence[Dict[str, Any]], circuity: float = 1.3,
                   improve: Optional[Sequence[Any]] = None,
                   exchange: Optional[Sequence[Any]] = None,
                   time_windows: Optional[Sequence[Any]] = None, T: Optional[np.ndarray] = None,
-                  tw_improve: Optional[Sequence[Any]] = None):
+                  tw_improve: Optional[Sequence[Any]] = None,
+                  shipment_improve: Optional[Sequence[Any]] = None):
     """``D``: given distance matrices [R, nm, nm] (road metres from the CCH router) instead of the
     haversine K5.  ``improve`` / ``exchange``: one flag per request; when either is given, returns
     ``(results, stats)``.  ``exchange`` implies ``improve`` (:mod:`routing.exchange`).
@@ -359,7 +384,11 @@ def batched_trips(requests: Sequence[Dict[str, Any]], circuity: float = 1.3,
     A ``time_windows`` entry ``(open_q, close_q, sv_q, pickup_from)`` (``pickup_from`` as
     :func:`shipments.parse_shipments` returns it) is a shipment request: planned by
     :mod:`routing.shipments` (on a GPU one launch, K6f); ``improve`` / ``exchange`` / ``tw_improve``
-    are ignored on it and its ``tw[k]`` is shaped like a time-window row's."""
+    are ignored on it and its ``tw[k]`` is shaped like a time-window row's.
+
+    ``shipment_improve``: one flag per request, honoured only on shipment rows: their trips are
+    improved by the unit-relocate search of :mod:`routing.shipment_improve` (on a GPU one more launch,
+    K6g, over the asking shipment rows only) and ``statistics["search"]`` holds what it did."""
     if time_windows is not None and (D is None) != (T is None):
         raise ValueError("time windows on given matrices need both D (metres) and T (seconds)")
     if not requests:
@@ -375,6 +404,7 @@ def batched_trips(requests: Sequence[Dict[str, Any]], circuity: float = 1.3,
         pd = pd if pd[1].any() else None
     if device is not None and torch.device(device).type == "cuda":
         return batched_trips_device(*packed, circuity=circuity, device=device, D=D, improve=improve,
-                                    exchange=exchange, tw=tw, T=T, tw_improve=tw_improve, pd=pd)
+                                    exchange=exchange, tw=tw, T=T, tw_improve=tw_improve, pd=pd,
+                                    shipment_improve=shipment_improve)
     return batched_trips_cpu(*packed, circuity=circuity, D=D, improve=improve, exchange=exchange, tw=tw, T=T,
-                             tw_improve=tw_improve, pd=pd)
+                             tw_improve=tw_improve, pd=pd, shipment_improve=shipment_improve)

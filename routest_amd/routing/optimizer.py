@@ -25,6 +25,8 @@ by the window-aware local search of :mod:`routing.tw_improve`; any other request
 A destination carrying ``"pickup_from": p`` makes a multi-stop request a shipment request
 (:mod:`routing.shipments`): pickup -> delivery pairs and plain stops planned by cheapest insertion
 of units under the windows; ``improve`` / ``exchange`` / ``tw_improve`` are ignored there.
+``"shipment_improve": true`` (same rule) on a shipment request improves those trips by the
+unit-relocate search of :mod:`routing.shipment_improve`; any other request ignores it.
 The batched GPU path for many concurrent requests (K5 + K6) is :func:`optimize_many`.
 """
 from __future__ import annotations
@@ -41,6 +43,7 @@ from .timewindows import (NEEDS_MATRIX_TIMES, parse_time_windows, schedule_prope
                           wants_time_windows)
 from .shipments import (NEEDS_MATRIX_TIMES as PD_NEEDS_MATRIX_TIMES, parse_shipments, pd_trips,
                         shipment_properties, wants_shipments)
+from .shipment_improve import pd_improve_trips, wants_shipment_improve
 from .tw_improve import tw_improve_trips, wants_tw_improve
 
 
@@ -124,7 +127,8 @@ def assemble_trips(provider, all_points: List[Dict[str, Any]], trips: List[List[
 def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, Any],
                trips: Optional[List[List[int]]] = None, ctx=None, improve: bool = False,
                improvement: Optional[Dict[str, int]] = None, exchange: bool = False,
-               tw=None, tw_result=None, tw_improve: bool = False, pd=None) -> Dict[str, Any]:
+               tw=None, tw_result=None, tw_improve: bool = False, pd=None,
+               shipment_improve: bool = False) -> Dict[str, Any]:
     """``improve``: re-sequence the trips built here (routing/improve.py); ``exchange``: also move
     stops between them (routing/exchange.py; it implies ``improve``).  Trips given by the caller
     are taken as they are; ``improvement`` holds their statistics if they were improved.
@@ -134,7 +138,8 @@ def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, A
     ``tw_improve``: the trips built here under the windows are improved (routing/tw_improve.py).
     ``pd``: the request's ``pickup_from`` per point (routing/shipments.py; it comes with ``tw``): the
     trips hold pickup -> delivery pairs, ``tw_improve`` is ignored as well and the response also
-    carries ``shipments``."""
+    carries ``shipments``.  ``shipment_improve``: the trips built here for a shipment request are
+    improved by the unit-relocate search (routing/shipment_improve.py)."""
     all_points = [source] + list(destinations)
     demand = [0.0] + [_float(p.get("payload", 0), 0.0) for p in destinations]
     if tw is not None and tw_result is None:
@@ -157,6 +162,11 @@ def multi_stop(provider, source, destinations, profile: str, driver: Dict[str, A
             trips, schedule, search = tw_improve_trips(
                 d, sec, trips, demand, _float(driver.get("vehicle_capacity", 9e12), 9e12),
                 _float(driver.get("maximum_distance", 9e12), 9e12), *tw)
+            tstats = dict(tstats, trips=len(trips), search=search)
+        if shipment_improve and pd is not None:
+            trips, schedule, search = pd_improve_trips(
+                d, sec, trips, demand, _float(driver.get("vehicle_capacity", 9e12), 9e12),
+                _float(driver.get("maximum_distance", 9e12), 9e12), *tw, pd)
             tstats = dict(tstats, trips=len(trips), search=search)
         tw_result = (schedule, tstats)
     if tw is not None:
@@ -258,7 +268,8 @@ def _optimize(input_data, provider, engine, trips, ctx, improvement, driver, veh
     feature = multi_stop(provider, source, destinations, profile, driver, trips, ctx,
                          improve=wants_improve(input_data), improvement=improvement,
                          exchange=wants_exchange(input_data), tw=tw, tw_result=tw_result,
-                         tw_improve=wants_tw_improve(input_data), pd=pd)
+                         tw_improve=wants_tw_improve(input_data), pd=pd,
+                         shipment_improve=wants_shipment_improve(input_data))
     if "error" in feature:
         return feature
     _annotate(feature, driver, vehicle_type, engine)
@@ -281,7 +292,8 @@ def optimize_many(requests: Sequence[Dict[str, Any]], provider, engine: str = "b
         # time-window requests (routing/timewindows.py) ride in the same batch; a malformed one is
         # left out here and answered with its error by optimize_route below
         tws = [_tw_or_none(requests[i]) for i in multi]
-        kw = ({"time_windows": tws, "tw_improve": [wants_tw_improve(requests[i]) for i in multi]}
+        kw = ({"time_windows": tws, "tw_improve": [wants_tw_improve(requests[i]) for i in multi],
+               "shipment_improve": [wants_shipment_improve(requests[i]) for i in multi]}
               if any(v is not None for v in tws) else {})
         got = batched_trips([requests[i] for i in multi], circuity=provider.circuity,
                             device=device, improve=[wants_improve(requests[i]) for i in multi],

@@ -40,6 +40,7 @@ from .batched import batched_trips
 from .greedy import InfeasibleStops
 from .exchange import wants_exchange
 from .improve import wants_improve
+from .shipment_improve import wants_shipment_improve
 from .tw_improve import wants_tw_improve
 from .optimizer import _tw_or_none, optimize_route
 from .providers import ProviderError
@@ -219,7 +220,8 @@ class RouteBatcher:
                 D[i, :n, :n] = met
                 if T is not None:
                     T[i, :n, :n] = sec
-            kw = ({"time_windows": tw, "T": T, "tw_improve": [wants_tw_improve(payloads[k]) for k in multi]}
+            kw = ({"time_windows": tw, "T": T, "tw_improve": [wants_tw_improve(payloads[k]) for k in multi],
+                   "shipment_improve": [wants_shipment_improve(payloads[k]) for k in multi]}
                   if T is not None else {})
             got = batched_trips([payloads[k] for k in multi], device=device, D=D,
                                 improve=[wants_improve(payloads[k]) for k in multi],
@@ -305,7 +307,8 @@ class RouteBatcher:
             # the haversine flush plans time-window and shipment requests too; the A* engine has no
             # seconds matrix, so there optimize_route answers them with its error
             tw = [_tw_or_none(payloads[k]) if name == "haversine" else None for k in multi]
-            kw = ({"time_windows": tw, "tw_improve": [wants_tw_improve(payloads[k]) for k in multi]}
+            kw = ({"time_windows": tw, "tw_improve": [wants_tw_improve(payloads[k]) for k in multi],
+                   "shipment_improve": [wants_shipment_improve(payloads[k]) for k in multi]}
                   if any(v is not None for v in tw) else {})
             got = batched_trips([payloads[k] for k in multi], circuity=self.provider.circuity,
                                 device=device, improve=[wants_improve(payloads[k]) for k in multi],

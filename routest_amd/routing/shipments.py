@@ -7,7 +7,8 @@ on board from leaving ``p`` until arriving at ``v``.  Entries in no pair stay *p
 at the depot, dropped at the stop.  A multi-stop request in which a destination carries the field
 is a *shipment request* and is planned by :func:`pd_trips`; ``time_window`` / ``service`` are
 honoured on every stop, ``improve`` / ``exchange`` / ``tw_improve`` are ignored (their moves take
-single stops and would split pairs).  Single-destination and ``alternatives`` requests ignore the
+single stops and would split pairs; ``shipment_improve`` asks for the search that moves whole units,
+:mod:`routing.shipment_improve`).  Single-destination and ``alternatives`` requests ignore the
 field.  The definition is schedule-independent, so this reference, the host C++ (``rtr::pd_trips``,
 ``csrc/runtime/route_core.h``) and the GPU kernel (K6f, ``csrc/route_pd.hip``) return the same
 trips, schedule and statistics, compared with ``==``.
@@ -428,11 +429,22 @@ def parse_shipments(payload) -> List[int]:
 def shipment_properties(schedule: Schedule, stats: Dict[str, int], close_q: Sequence[int], demand: Sequence[float],
                         pickup_from: Sequence[int]) -> Tuple[List[List[Dict[str, Any]]], Dict[str, Any], Dict[str, Any]]:
     """``(properties.schedule, properties.time_windows, properties.shipments)`` of a response: the
-    time-window properties, every schedule entry with its ``type`` and the ``load`` on leaving it."""
+    time-window properties, every schedule entry with its ``type`` and the ``load`` on leaving it.
+    With ``stats["search"]`` (the statistics of :mod:`routing.shipment_improve`) the second also
+    reports the local search."""
     n1 = len(pickup_from)
     kind, mate = kinds_of(pickup_from, n1)
     qd = [0] + [quantize(demand[s]) for s in range(1, n1)]
     out, info = schedule_properties(schedule, {k: v for k, v in stats.items() if k != "search"}, close_q)
+    search = stats.get("search")
+    if search is not None:
+        # the statistics of routing/shipment_improve.py: the schedule given here is the improved one
+        info = {"method": info["method"] + "+unit_relocate", "stops_with_windows": info["stops_with_windows"],
+                "trips": int(search["trips_after"]), "waiting": int(search["waiting_q"]) / 1000.0,
+                "moves": int(search["moves"]), "pair_moves": int(search["pair_moves"]),
+                "trips_before": int(search["trips_before"]),
+                "matrix_distance_before": int(search["len_before_q"]) / 1000.0,
+                "matrix_distance_after": int(search["len_after_q"]) / 1000.0}
     top = 0
     for rows, trip in zip(out, schedule):
         load = load_profile(qd, kind, mate, [0] + [s for s, _, _, _ in trip] + [0])
