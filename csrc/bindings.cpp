@@ -444,7 +444,8 @@ torch::Tensor route_haversine_matrix(torch::Tensor lat, torch::Tensor lon, torch
   return D;
 }
 
-// The checks the route bindings (K6, K6b-K6e) share; the message texts are part of the interface.
+// The checks the route bindings (K6, K6b-K6g) share; the message texts are part of the interface.
+// windowed_rows below adds what the four windowed ones (K6d-K6g) share beyond them.
 static void check_route_D(const torch::Tensor& D, const torch::Tensor* T = nullptr) {
   TORCH_CHECK(D.scalar_type() == torch::kFloat64 && D.dim() == 3 && D.size(1) == D.size(2),
               "D must be f64 [R,NM,NM]");
@@ -563,16 +564,19 @@ std::vector<torch::Tensor> route_exchange_trips(torch::Tensor D, torch::Tensor n
   return {moves, rejected, tbefore, tafter, before, after};
 }
 
-// K6d: rows with flag != 0 are planned under their time windows (routing/timewindows.py).  Returns
-// (visit, trip_of i32 [R,NM] in K6's layout, ntrips, status i32 [R], arrival_q, start_q i64 [R,NM]
-// per visit position, stats i64 [R,4] = insertions, rejected, len_q, waiting_q).  Rows with
-// flag == 0 keep the fill: -1 in the four [R,NM] outputs, 0 elsewhere.
-std::vector<torch::Tensor> route_tw_trips(torch::Tensor D, torch::Tensor T, torch::Tensor npts,
-                                          torch::Tensor demand, torch::Tensor cap, torch::Tensor maxd,
-                                          torch::Tensor open, torch::Tensor close, torch::Tensor service,
-                                          torch::Tensor flag) {
-  for (auto* t : {&D, &T, &npts, &demand, &cap, &maxd, &open, &close, &service, &flag})
-    check_dev(*t, "route tensor");
+// What the four windowed bindings (K6d-K6g) share: the checks of their common inputs, with the texts
+// they always had, and the launch arguments of those inputs; the outputs are the caller's to set.
+// windows: how the caller's message names open / close / service (K6e / K6g name arrival and start
+// in the same breath and check those two themselves).  The caller checks its own tensors' device
+// before the call, so every device check still comes first; its other checks now come behind
+// `flag`, so an input that is wrong in two ways may name the other fault first.
+static rt::WindowedRows windowed_rows(const torch::Tensor& D, const torch::Tensor& T, const torch::Tensor& npts,
+                                      const torch::Tensor& demand, const torch::Tensor& cap,
+                                      const torch::Tensor& maxd, const torch::Tensor& open,
+                                      const torch::Tensor& close, const torch::Tensor& service,
+                                      const torch::Tensor& flag,
+                                      const char* windows = "open, close and service") {
+  for (auto* t : {&D, &T, &npts, &demand, &cap, &maxd, &open, &close, &service, &flag}) check_dev(*t, "route tensor");
   check_route_D(D, &T);
   const int R = (int)D.size(0), NM = (int)D.size(1);
   TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
@@ -580,26 +584,65 @@ std::vector<torch::Tensor> route_tw_trips(torch::Tensor D, torch::Tensor T, torc
   check_route_rows({&demand}, torch::kFloat64, R, NM, "demand");
   check_route_vec(cap, torch::kFloat64, R, "cap");
   check_route_vec(maxd, torch::kFloat64, R, "maxd");
-  check_route_rows({&open, &close, &service}, torch::kInt64, R, NM, "open, close and service", " (milliseconds)");
+  check_route_rows({&open, &close, &service}, torch::kInt64, R, NM, windows, " (milliseconds)");
   check_route_vec(flag, torch::kUInt8, R, "flag");
+  rt::WindowedRows w = {};
+  w.D = D.data_ptr<double>();
+  w.T = T.data_ptr<double>();
+  w.npts = npts.data_ptr<int>();
+  w.demand = demand.data_ptr<double>();
+  w.cap = cap.data_ptr<double>();
+  w.maxd = maxd.data_ptr<double>();
+  w.open = (const long long*)open.data_ptr<int64_t>();
+  w.close = (const long long*)close.data_ptr<int64_t>();
+  w.service = (const long long*)service.data_ptr<int64_t>();
+  w.flag = flag.data_ptr<uint8_t>();
+  w.R = R;
+  w.NM = NM;
+  return w;
+}
+
+// the outputs of a windowed launch: a constructor's fresh ones, or a local search's own inputs
+static void windowed_outputs(rt::WindowedRows& w, torch::Tensor& visit, torch::Tensor& trip_of, torch::Tensor& ntrips,
+                             torch::Tensor& status, torch::Tensor& arrival, torch::Tensor& start,
+                             torch::Tensor& stats) {
+  w.visit = visit.data_ptr<int>();
+  w.trip_of = trip_of.data_ptr<int>();
+  w.ntrips = ntrips.data_ptr<int>();
+  w.status = status.data_ptr<int>();
+  w.arrival = (long long*)arrival.data_ptr<int64_t>();
+  w.start = (long long*)start.data_ptr<int64_t>();
+  w.stats = (long long*)stats.data_ptr<int64_t>();
+}
+
+// K6d / K6f: the outputs of a construction, filled as for a row with flag == 0, and its launch.
+// Returns (visit, trip_of i32 [R,NM] in K6's layout, ntrips, status i32 [R], arrival_q, start_q i64
+// [R,NM] per visit position, stats i64 [R,4] = insertions, rejected, len_q, waiting_q).  Rows with
+// flag == 0 keep the fill: -1 in the four [R,NM] outputs, 0 elsewhere.
+static std::vector<torch::Tensor> windowed_construct(rt::WindowedRows w, const torch::Tensor& D,
+                                                     hipError_t (*launch)(const rt::WindowedRows&, hipStream_t)) {
   const c10::DeviceGuard guard(D.device());
   auto iopt = D.options().dtype(torch::kInt32);
   auto lopt = D.options().dtype(torch::kInt64);
-  auto visit = torch::full({R, NM}, -1, iopt);
-  auto trip_of = torch::full({R, NM}, -1, iopt);
-  auto ntrips = torch::zeros({R}, iopt);
-  auto status = torch::zeros({R}, iopt);
-  auto arrival = torch::full({R, NM}, -1, lopt);
-  auto start = torch::full({R, NM}, -1, lopt);
-  auto stats = torch::zeros({R, 4}, lopt);
-  RT_CHECK_HIP(rt::launch_tw_trips(
-      D.data_ptr<double>(), T.data_ptr<double>(), npts.data_ptr<int>(), demand.data_ptr<double>(),
-      cap.data_ptr<double>(), maxd.data_ptr<double>(), (const long long*)open.data_ptr<int64_t>(),
-      (const long long*)close.data_ptr<int64_t>(), (const long long*)service.data_ptr<int64_t>(),
-      flag.data_ptr<uint8_t>(), R, NM, visit.data_ptr<int>(), trip_of.data_ptr<int>(), ntrips.data_ptr<int>(),
-      status.data_ptr<int>(), (long long*)arrival.data_ptr<int64_t>(), (long long*)start.data_ptr<int64_t>(),
-      (long long*)stats.data_ptr<int64_t>(), cur_stream(D)));
+  auto visit = torch::full({w.R, w.NM}, -1, iopt);
+  auto trip_of = torch::full({w.R, w.NM}, -1, iopt);
+  auto ntrips = torch::zeros({w.R}, iopt);
+  auto status = torch::zeros({w.R}, iopt);
+  auto arrival = torch::full({w.R, w.NM}, -1, lopt);
+  auto start = torch::full({w.R, w.NM}, -1, lopt);
+  auto stats = torch::zeros({w.R, 4}, lopt);
+  windowed_outputs(w, visit, trip_of, ntrips, status, arrival, start, stats);
+  RT_CHECK_HIP(launch(w, cur_stream(D)));
   return {visit, trip_of, ntrips, status, arrival, start, stats};
+}
+
+// K6d: rows with flag != 0 are planned under their time windows (routing/timewindows.py).
+std::vector<torch::Tensor> route_tw_trips(torch::Tensor D, torch::Tensor T, torch::Tensor npts,
+                                          torch::Tensor demand, torch::Tensor cap, torch::Tensor maxd,
+                                          torch::Tensor open, torch::Tensor close, torch::Tensor service,
+                                          torch::Tensor flag) {
+  const rt::WindowedRows w = windowed_rows(D, T, npts, demand, cap, maxd, open, close, service, flag);
+  return windowed_construct(w, D, rt::launch_tw_trips);
 }
 
 // K6f: rows with flag != 0 are planned as shipment requests (routing/shipments.py): plain stops and
@@ -610,37 +653,11 @@ std::vector<torch::Tensor> route_pd_trips(torch::Tensor D, torch::Tensor T, torc
                                           torch::Tensor demand, torch::Tensor cap, torch::Tensor maxd,
                                           torch::Tensor open, torch::Tensor close, torch::Tensor service,
                                           torch::Tensor pickup_from, torch::Tensor flag) {
-  for (auto* t : {&D, &T, &npts, &demand, &cap, &maxd, &open, &close, &service, &pickup_from, &flag})
-    check_dev(*t, "route tensor");
-  check_route_D(D, &T);
-  const int R = (int)D.size(0), NM = (int)D.size(1);
-  TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
-  check_route_vec(npts, torch::kInt32, R, "npts");
-  check_route_rows({&demand}, torch::kFloat64, R, NM, "demand");
-  check_route_vec(cap, torch::kFloat64, R, "cap");
-  check_route_vec(maxd, torch::kFloat64, R, "maxd");
-  check_route_rows({&open, &close, &service}, torch::kInt64, R, NM, "open, close and service", " (milliseconds)");
-  check_route_rows({&pickup_from}, torch::kInt32, R, NM, "pickup_from");
-  check_route_vec(flag, torch::kUInt8, R, "flag");
-  const c10::DeviceGuard guard(D.device());
-  auto iopt = D.options().dtype(torch::kInt32);
-  auto lopt = D.options().dtype(torch::kInt64);
-  auto visit = torch::full({R, NM}, -1, iopt);
-  auto trip_of = torch::full({R, NM}, -1, iopt);
-  auto ntrips = torch::zeros({R}, iopt);
-  auto status = torch::zeros({R}, iopt);
-  auto arrival = torch::full({R, NM}, -1, lopt);
-  auto start = torch::full({R, NM}, -1, lopt);
-  auto stats = torch::zeros({R, 4}, lopt);
-  RT_CHECK_HIP(rt::launch_pd_trips(
-      D.data_ptr<double>(), T.data_ptr<double>(), npts.data_ptr<int>(), demand.data_ptr<double>(),
-      cap.data_ptr<double>(), maxd.data_ptr<double>(), (const long long*)open.data_ptr<int64_t>(),
-      (const long long*)close.data_ptr<int64_t>(), (const long long*)service.data_ptr<int64_t>(),
-      pickup_from.data_ptr<int>(), flag.data_ptr<uint8_t>(), R, NM, visit.data_ptr<int>(),
-      trip_of.data_ptr<int>(), ntrips.data_ptr<int>(), status.data_ptr<int>(),
-      (long long*)arrival.data_ptr<int64_t>(), (long long*)start.data_ptr<int64_t>(),
-      (long long*)stats.data_ptr<int64_t>(), cur_stream(D)));
-  return {visit, trip_of, ntrips, status, arrival, start, stats};
+  check_dev(pickup_from, "route tensor");
+  rt::WindowedRows w = windowed_rows(D, T, npts, demand, cap, maxd, open, close, service, flag);
+  check_route_rows({&pickup_from}, torch::kInt32, w.R, w.NM, "pickup_from");
+  w.pickup_from = pickup_from.data_ptr<int>();
+  return windowed_construct(w, D, rt::launch_pd_trips);
 }
 
 // K6e on K6d's own outputs: visit / trip_of / ntrips / arrival / start are rewritten in place for
@@ -651,31 +668,17 @@ torch::Tensor route_tw_improve(torch::Tensor D, torch::Tensor T, torch::Tensor n
                                torch::Tensor service, torch::Tensor visit, torch::Tensor trip_of,
                                torch::Tensor ntrips, torch::Tensor status, torch::Tensor arrival,
                                torch::Tensor start, torch::Tensor flag) {
-  for (auto* t : {&D, &T, &npts, &demand, &cap, &maxd, &open, &close, &service, &visit, &trip_of, &ntrips, &status,
-                  &arrival, &start, &flag})
-    check_dev(*t, "route tensor");
-  check_route_D(D, &T);
-  const int R = (int)D.size(0), NM = (int)D.size(1);
-  TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
-  check_route_vec(npts, torch::kInt32, R, "npts");
-  check_route_rows({&demand}, torch::kFloat64, R, NM, "demand");
-  check_route_vec(cap, torch::kFloat64, R, "cap");
-  check_route_vec(maxd, torch::kFloat64, R, "maxd");
-  check_route_rows({&open, &close, &service, &arrival, &start}, torch::kInt64, R, NM,
-                   "open, close, service, arrival and start", " (milliseconds)");
-  check_route_rows({&visit, &trip_of}, torch::kInt32, R, NM, "visit and trip_of");
-  check_route_vec(ntrips, torch::kInt32, R, "ntrips");
-  check_route_vec(status, torch::kInt32, R, "status");
-  check_route_vec(flag, torch::kUInt8, R, "flag");
+  for (auto* t : {&visit, &trip_of, &ntrips, &status, &arrival, &start}) check_dev(*t, "route tensor");
+  const char* windows = "open, close, service, arrival and start";
+  rt::WindowedRows w = windowed_rows(D, T, npts, demand, cap, maxd, open, close, service, flag, windows);
+  check_route_rows({&arrival, &start}, torch::kInt64, w.R, w.NM, windows, " (milliseconds)");
+  check_route_rows({&visit, &trip_of}, torch::kInt32, w.R, w.NM, "visit and trip_of");
+  check_route_vec(ntrips, torch::kInt32, w.R, "ntrips");
+  check_route_vec(status, torch::kInt32, w.R, "status");
   const c10::DeviceGuard guard(D.device());
-  auto stats = torch::zeros({R, 7}, D.options().dtype(torch::kInt64));
-  RT_CHECK_HIP(rt::launch_tw_improve(
-      D.data_ptr<double>(), T.data_ptr<double>(), npts.data_ptr<int>(), demand.data_ptr<double>(),
-      cap.data_ptr<double>(), maxd.data_ptr<double>(), (const long long*)open.data_ptr<int64_t>(),
-      (const long long*)close.data_ptr<int64_t>(), (const long long*)service.data_ptr<int64_t>(),
-      flag.data_ptr<uint8_t>(), R, NM, visit.data_ptr<int>(), trip_of.data_ptr<int>(), ntrips.data_ptr<int>(),
-      status.data_ptr<int>(), (long long*)arrival.data_ptr<int64_t>(), (long long*)start.data_ptr<int64_t>(),
-      (long long*)stats.data_ptr<int64_t>(), cur_stream(D)));
+  auto stats = torch::zeros({w.R, 7}, D.options().dtype(torch::kInt64));
+  windowed_outputs(w, visit, trip_of, ntrips, status, arrival, start, stats);
+  RT_CHECK_HIP(rt::launch_tw_improve(w, cur_stream(D)));
   return stats;
 }
 
@@ -688,32 +691,18 @@ torch::Tensor route_pd_improve(torch::Tensor D, torch::Tensor T, torch::Tensor n
                                torch::Tensor service, torch::Tensor pickup_from, torch::Tensor visit,
                                torch::Tensor trip_of, torch::Tensor ntrips, torch::Tensor status,
                                torch::Tensor arrival, torch::Tensor start, torch::Tensor flag) {
-  for (auto* t : {&D, &T, &npts, &demand, &cap, &maxd, &open, &close, &service, &pickup_from, &visit, &trip_of,
-                  &ntrips, &status, &arrival, &start, &flag})
-    check_dev(*t, "route tensor");
-  check_route_D(D, &T);
-  const int R = (int)D.size(0), NM = (int)D.size(1);
-  TORCH_CHECK(NM >= 1 && NM <= 4096, "at most 4095 stops per request");
-  check_route_vec(npts, torch::kInt32, R, "npts");
-  check_route_rows({&demand}, torch::kFloat64, R, NM, "demand");
-  check_route_vec(cap, torch::kFloat64, R, "cap");
-  check_route_vec(maxd, torch::kFloat64, R, "maxd");
-  check_route_rows({&open, &close, &service, &arrival, &start}, torch::kInt64, R, NM,
-                   "open, close, service, arrival and start", " (milliseconds)");
-  check_route_rows({&pickup_from, &visit, &trip_of}, torch::kInt32, R, NM, "pickup_from, visit and trip_of");
-  check_route_vec(ntrips, torch::kInt32, R, "ntrips");
-  check_route_vec(status, torch::kInt32, R, "status");
-  check_route_vec(flag, torch::kUInt8, R, "flag");
+  for (auto* t : {&pickup_from, &visit, &trip_of, &ntrips, &status, &arrival, &start}) check_dev(*t, "route tensor");
+  const char* windows = "open, close, service, arrival and start";
+  rt::WindowedRows w = windowed_rows(D, T, npts, demand, cap, maxd, open, close, service, flag, windows);
+  check_route_rows({&arrival, &start}, torch::kInt64, w.R, w.NM, windows, " (milliseconds)");
+  check_route_rows({&pickup_from, &visit, &trip_of}, torch::kInt32, w.R, w.NM, "pickup_from, visit and trip_of");
+  check_route_vec(ntrips, torch::kInt32, w.R, "ntrips");
+  check_route_vec(status, torch::kInt32, w.R, "status");
+  w.pickup_from = pickup_from.data_ptr<int>();
   const c10::DeviceGuard guard(D.device());
-  auto stats = torch::zeros({R, 8}, D.options().dtype(torch::kInt64));
-  RT_CHECK_HIP(rt::launch_pd_improve(
-      D.data_ptr<double>(), T.data_ptr<double>(), npts.data_ptr<int>(), demand.data_ptr<double>(),
-      cap.data_ptr<double>(), maxd.data_ptr<double>(), (const long long*)open.data_ptr<int64_t>(),
-      (const long long*)close.data_ptr<int64_t>(), (const long long*)service.data_ptr<int64_t>(),
-      pickup_from.data_ptr<int>(), flag.data_ptr<uint8_t>(), R, NM, visit.data_ptr<int>(),
-      trip_of.data_ptr<int>(), ntrips.data_ptr<int>(), status.data_ptr<int>(),
-      (long long*)arrival.data_ptr<int64_t>(), (long long*)start.data_ptr<int64_t>(),
-      (long long*)stats.data_ptr<int64_t>(), cur_stream(D)));
+  auto stats = torch::zeros({w.R, 8}, D.options().dtype(torch::kInt64));
+  windowed_outputs(w, visit, trip_of, ntrips, status, arrival, start, stats);
+  RT_CHECK_HIP(rt::launch_pd_improve(w, cur_stream(D)));
   return stats;
 }
 

@@ -230,53 +230,46 @@ hipError_t launch_improve_trips(const double* D, const int* npts, const double* 
                                 long long* len_before_q, long long* len_after_q,
                                 hipStream_t stream);
 
-// ---- K6d cheapest-insertion trips under time windows : route_tw.hip ----
-// Rows with flag != 0 are planned (routing/timewindows.py): visit / trip_of in K6's layout, ntrips,
-// status (0 ok, 1 a stop cannot be served alone: visit lists the stops that can, 2 more than 128
-// stops), arrival / start milliseconds per visit position, stats [R, 4] = insertions, rejected,
-// len_q, waiting_q.  Rows with flag == 0 are not touched.  open / close / service: [R, NM] int64
-// milliseconds per point (column 0 ignored), 0 <= open, service <= 2^31, 0 <= close <= 2^62.
-hipError_t launch_tw_trips(const double* D, const double* T, const int* npts, const double* demand,
-                           const double* cap, const double* maxd, const long long* open,
-                           const long long* close, const long long* service, const unsigned char* flag,
-                           int R, int NM, int* visit, int* trip_of, int* ntrips, int* status,
-                           long long* arrival, long long* start, long long* stats, hipStream_t stream);
+// ---- the windowed trip stages K6d-K6g : route_tw / route_pd / route_tw_improve / route_pd_improve .hip ----
+// What the four launches take (the kernels' side of it is route_windows.h).  D, T: [R, NM, NM] metres
+// and seconds; demand [R, NM]; cap, maxd [R]; open / close / service: [R, NM] int64 milliseconds per
+// point (column 0 ignored), 0 <= open, service <= 2^31, 0 <= close <= 2^62; pickup_from [R, NM] int32
+// per point (column 0 ignored): the point index of a delivery's pickup, negative for none (K6f / K6g;
+// null for K6d / K6e); flag [R]: rows with flag == 0 are not touched.  visit / trip_of in K6's
+// layout, ntrips, arrival / start milliseconds per visit position, stats [R, 4 | 7 | 8] per stage.
+struct WindowedRows {
+  const double *D, *T;
+  const int* npts;
+  const double *demand, *cap, *maxd;
+  const long long *open, *close, *service;
+  const int* pickup_from;
+  const unsigned char* flag;
+  int R, NM;
+  int *visit, *trip_of, *ntrips;
+  int* status;  // written by K6d / K6f; K6e / K6g only read it
+  long long *arrival, *start, *stats;
+};
 
-// ---- K6f cheapest insertion of plain stops and pickup -> delivery pairs : route_pd.hip ----
-// Rows with flag != 0 are planned (routing/shipments.py); inputs and outputs as launch_tw_trips, and
-// pickup_from [R, NM] int32 per point (column 0 ignored): the point index of a delivery's pickup,
-// negative for none.  status 3: a malformed pickup_from (not another stop of the row, itself a
-// delivery, or the pickup of two deliveries).  Rows with flag == 0 are not touched.
-hipError_t launch_pd_trips(const double* D, const double* T, const int* npts, const double* demand,
-                           const double* cap, const double* maxd, const long long* open,
-                           const long long* close, const long long* service, const int* pickup_from,
-                           const unsigned char* flag, int R, int NM, int* visit, int* trip_of, int* ntrips,
-                           int* status, long long* arrival, long long* start, long long* stats,
-                           hipStream_t stream);
+// K6d cheapest-insertion trips under time windows (routing/timewindows.py): rows with flag != 0 are
+// planned; status 0 ok, 1 a stop cannot be served alone: visit lists the stops that can, 2 more than
+// 128 stops; stats [R, 4] = insertions, rejected, len_q, waiting_q.
+hipError_t launch_tw_trips(const WindowedRows& rows, hipStream_t stream);
 
-// ---- K6e window-aware relocate / swap on K6d's outputs : route_tw_improve.hip ----
-// visit, trip_of, ntrips, arrival and start are rewritten in place for rows with flag != 0 and
-// status == 0 (routing/tw_improve.py; still grouped by trip, trip indices compacted) and their
-// stats [R, 7] = moves, rejected, trips_before, trips_after, len_before_q, len_after_q, waiting_q
-// are written; every other row and its stats are not touched.  Inputs as launch_tw_trips takes them.
-hipError_t launch_tw_improve(const double* D, const double* T, const int* npts, const double* demand,
-                             const double* cap, const double* maxd, const long long* open,
-                             const long long* close, const long long* service, const unsigned char* flag,
-                             int R, int NM, int* visit, int* trip_of, int* ntrips, const int* status,
-                             long long* arrival, long long* start, long long* stats, hipStream_t stream);
+// K6f cheapest insertion of plain stops and pickup -> delivery pairs (routing/shipments.py): as
+// launch_tw_trips, and status 3: a malformed pickup_from (not another stop of the row, itself a
+// delivery, or the pickup of two deliveries).
+hipError_t launch_pd_trips(const WindowedRows& rows, hipStream_t stream);
 
-// ---- K6g unit relocate on K6f's outputs : route_pd_improve.hip ----
-// visit, trip_of, ntrips, arrival and start are rewritten in place for rows with flag != 0 and
-// status == 0 (routing/shipment_improve.py; still grouped by trip, trip indices compacted) and their
+// K6e window-aware relocate / swap on K6d's outputs (routing/tw_improve.py): visit, trip_of, ntrips,
+// arrival and start are rewritten in place for rows with flag != 0 and status == 0 (still grouped by
+// trip, trip indices compacted) and their stats [R, 7] = moves, rejected, trips_before, trips_after,
+// len_before_q, len_after_q, waiting_q are written; every other row and its stats are not touched.
+hipError_t launch_tw_improve(const WindowedRows& rows, hipStream_t stream);
+
+// K6g unit relocate on K6f's outputs (routing/shipment_improve.py): as launch_tw_improve, with
 // stats [R, 8] = moves, pair_moves, rejected, trips_before, trips_after, len_before_q, len_after_q,
-// waiting_q are written; every other row and its stats are not touched.  Inputs as launch_pd_trips
-// takes them.
-hipError_t launch_pd_improve(const double* D, const double* T, const int* npts, const double* demand,
-                             const double* cap, const double* maxd, const long long* open,
-                             const long long* close, const long long* service, const int* pickup_from,
-                             const unsigned char* flag, int R, int NM, int* visit, int* trip_of, int* ntrips,
-                             const int* status, long long* arrival, long long* start, long long* stats,
-                             hipStream_t stream);
+// waiting_q.
+hipError_t launch_pd_improve(const WindowedRows& rows, hipStream_t stream);
 
 // ---- K6c inter-trip relocate / swap on K6's outputs : route_exchange.hip ----
 // visit, trip_of and ntrips are rewritten in place for rows with flag != 0 and status == 0 (still

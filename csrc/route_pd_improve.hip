@@ -6,10 +6,15 @@
 // move types with K6f's (i, j) position convention; best-improvement selection with the
 // (type, A, x, B, i, j) tie rule; the f64 acceptance walks; the move cap and the skip conditions) and
 // the fast tests evaluated here are in routest_amd/routing/shipment_improve.py; the host C++ is
-// rtr::pd_improve_trips (runtime/route_core.h).  All three are compared with ==: every quantity the
+// rtr::pd_improve_trips (runtime/route_trips.h).  All three are compared with ==: every quantity the
 // search orders by is an int64 sum, so the schedule below cannot change it.
 //
-// One TEAM of threads per request row (teams, tiers and the barrier discipline: route_team.h).
+// One TEAM of threads per request row (teams, tiers and the barrier discipline: route_team.h).  What
+// K6g shares with K6d-K6f (the launch arguments, the LDS prefix and its view, the gather, kinds and
+// mates, the row as the constructor left it, the walks over one trip and the f64 acceptance walks)
+// is in route_windows.h.  The type-0 scan keeps its own copy of K6f's pricing of one unit at one
+// position: shared with K6f, it put this kernel's small tier over the speed bound in the one visit
+// that measured it (profiles/route_windows_refactor.md).
 //
 // The LDS is K6e's image (both quantized matrices as int32, gathered once; open / close / service /
 // demand; route_team.h's flat order in two copies; dep[] and z[] per flat position; Lq per trip)
@@ -34,8 +39,7 @@
 //      parallel and four lanes, one per walk, add them in order (the only place where float
 //      association matters); accepted: the copies change roles; rejected: the search ends.
 // At the end the non-empty trips are compacted as in K6e.
-#include "ops.h"
-#include "route_team.h"
+#include "route_windows.h"
 
 namespace rt {
 
@@ -43,24 +47,15 @@ namespace {
 
 using namespace team;
 
-constexpr int kPlain = 0, kPickup = 1, kDelivery = 2;
-
 // LDS of one team (offsets in bytes), for a stop capacity of kc; [2]: two arrays of stride v8 / v4
 struct PdImproveLds {
-  size_t Q = 0, T = 0, open = 0, close = 0, sv = 0, qd = 0, dep = 0, z = 0, load = 0, pm = 0, Lq = 0, ld0 = 0,
-         rem = 0, dv = 0, dm = 0, ord = 0, tof = 0, tst = 0, cnt = 0, pos = 0, kind = 0, mate = 0, uw = 0, snd = 0,
-         rank = 0, bnd = 0, redg = 0, redc = 0, misc = 0, bytes = 0;
+  WindowLds w;  // dep, z: per flat position, the departure and the latest start of its stop
+  size_t load = 0, pm = 0, Lq = 0, ld0 = 0, rem = 0, dv = 0, dm = 0, ord = 0, tof = 0, tst = 0, cnt = 0, pos = 0,
+         kind = 0, mate = 0, uw = 0, snd = 0, rank = 0, bnd = 0, redg = 0, redc = 0, misc = 0, bytes = 0;
   int v8 = 0, v4 = 0;
   __host__ __device__ constexpr explicit PdImproveLds(int kc) {
     LdsCarve c;
-    Q = c.take(4, (size_t)(kc + 1) * matrix_stride(kc));
-    T = c.take(4, (size_t)(kc + 1) * matrix_stride(kc));
-    open = c.take(8, kc + 4);
-    close = c.take(8, kc + 4);
-    sv = c.take(8, kc + 4);
-    qd = c.take(8, kc + 4);
-    dep = c.take(8, kc + 4);     // per flat position: the departure of its stop
-    z = c.take(8, kc + 4);       // per flat position: the latest start of its stop
+    w = WindowLds(c, kc);
     load = c.take(8, kc + 4);    // per flat position: the load on leaving its stop
     pm = c.take(8, kc + 4);      // per flat position: the largest load of its trip up to here
     Lq = c.take(8, kc + 4);      // per trip
@@ -89,12 +84,9 @@ struct PdImproveLds {
 };
 static_assert(PdImproveLds(32).bytes == 15648 && PdImproveLds(128).bytes == 157728, "the layout is fixed");
 
-// what the per-lane walks read: the team's LDS arrays of the current order
-struct PdView {
-  const int *sQ, *sT;
-  const long long *open, *close, *sv, *qd;
+// what the per-lane walks read: the windowed view, kinds and mates, and the current order
+struct PdView : WindowView {
   const int *kind, *mate, *ord;
-  int S;
   long long cap_q;
 };
 
@@ -159,33 +151,21 @@ __device__ __forceinline__ long long pd_move_code(int type, int A, int x, int B,
 // KC: stop capacity of the LDS carve (the launch sizes the dynamic region for it).  It must stay the
 // first parameter: launch_two_tiers passes it there, in front of the launch's own arguments.
 template <int TEAM>
-__global__ __launch_bounds__(Team<TEAM>::BLOCK) void pd_improve_kernel(
-    int KC, const double* __restrict__ D, const double* __restrict__ T, const int* __restrict__ npts,
-    const double* __restrict__ demand, const double* __restrict__ cap, const double* __restrict__ maxd,
-    const long long* __restrict__ open, const long long* __restrict__ close,
-    const long long* __restrict__ service, const int* __restrict__ pickup_from,
-    const unsigned char* __restrict__ flag, int R, int NM, int* __restrict__ visit, int* __restrict__ trip_of,
-    int* __restrict__ ntrips, const int* __restrict__ status, long long* __restrict__ arrival,
-    long long* __restrict__ start, long long* __restrict__ stats) {
+__global__ __launch_bounds__(Team<TEAM>::BLOCK) void pd_improve_kernel(int KC, const WindowedRows rows) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   using Tm = Team<TEAM>;
-  const Row rw = Tm::row(npts, R, NM);
+  const Row rw = Tm::row(rows.npts, rows.R, rows.NM);
   if (!rw.mine) return;
-  const int tid = rw.tid, r = rw.r, n = rw.n, ns = rw.ns;
-  if (flag[r] == 0 || status[r] != 0) return;  // not asked for, or not planned: nothing is touched
+  const int tid = rw.tid, r = rw.r, n = rw.n, ns = rw.ns, NM = rows.NM;
+  if (rows.flag[r] == 0 || rows.status[r] != 0) return;  // not asked for, or not planned: nothing is touched
   if (ns == 0 || ns > kMaxStops || ns > KC) return;
 
   const PdImproveLds L(KC);
   unsigned char* base = smem + (size_t)rw.team * L.bytes;
-  const int S = matrix_stride(KC), V4 = L.v4, V8 = L.v8;
-  int* sQ = (int*)(base + L.Q);
-  int* sT = (int*)(base + L.T);
-  long long* s_open = (long long*)(base + L.open);
-  long long* s_close = (long long*)(base + L.close);
-  long long* s_sv = (long long*)(base + L.sv);
-  long long* s_qd = (long long*)(base + L.qd);
-  long long* s_dep = (long long*)(base + L.dep);
-  long long* s_z = (long long*)(base + L.z);
+  const WindowView vw = window_view(base, L.w, KC);
+  const int S = vw.S, V4 = L.v4, V8 = L.v8;
+  int *sQ = vw.sQ, *sT = vw.sT;
+  long long *s_open = vw.open, *s_close = vw.close, *s_sv = vw.sv, *s_qd = vw.qd, *s_dep = vw.dep, *s_z = vw.z;
   long long* s_load = (long long*)(base + L.load);
   long long* s_pm = (long long*)(base + L.pm);
   long long* s_Lq = (long long*)(base + L.Lq);
@@ -206,50 +186,23 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void pd_improve_kernel(
   long long* s_redc = (long long*)(base + L.redc);
   int* s_misc = (int*)(base + L.misc);
 
-  const double* d = D + (size_t)r * NM * NM;
-  const double* t = T + (size_t)r * NM * NM;
-  const double* dem = demand + (size_t)r * NM;
-  const long long* op = open + (size_t)r * NM;
-  const long long* cl = close + (size_t)r * NM;
-  const long long* sv = service + (size_t)r * NM;
-  const int* pf = pickup_from + (size_t)r * NM;
-  int* vrow = visit + (size_t)r * NM;
-  int* trow = trip_of + (size_t)r * NM;
-  long long* arow = arrival + (size_t)r * NM;
-  long long* strow = start + (size_t)r * NM;
-  long long* srow = stats + (size_t)r * 8;
-  const double MD = maxd[r], CAP = cap[r];
-  const long long cap_q = quantize_limit(CAP), max_q = quantize_limit(MD);
+  const WindowRow row = window_row(rows, r);
+  const double *d = row.d, *dem = row.dem;
+  int *vrow = row.vrow, *trow = row.trow;
+  long long* srow = rows.stats + (size_t)r * 8;
+  const double MD = row.MD, CAP = row.CAP;
+  const long long cap_q = row.cap_q, max_q = row.max_q;
 
   // ---- the row as K6f left it, from global memory: its trips, its waiting time, its validity
-  long long groups = 0, wait0 = 0, badv = 0;
-  for (int p = tid; p < ns; p += TEAM) {
-    const int v = vrow[p];
-    badv += (v < 1 || v >= n) ? 1 : 0;
-    groups += (p == 0 || trow[p] != trow[p - 1]) ? 1 : 0;
-    wait0 += strow[p] - arow[p];
-  }
-  const int m = (int)Tm::sum(groups, s_redg, tid);
-  wait0 = Tm::sum(wait0, s_redg, tid);
-  if (Tm::sum(badv, s_redg, tid) != 0) return;  // not K6f's output: leave the row alone
+  int m;
+  long long wait0;
+  if (!left_by_constructor<TEAM>(row, n, ns, s_redg, tid, m, wait0)) return;  // not K6f's output
 
   // ---- gather: both quantized matrices, the per-stop vectors, kinds and mates, the order
-  for (int c = tid; c < n * n; c += TEAM) {
-    const int a = c / n, b = c - a * n;
-    sQ[a * S + b] = quantize_entry(d[(size_t)a * NM + b]);
-    sT[a * S + b] = quantize_entry(t[(size_t)a * NM + b]);
-  }
-  for (int s = tid; s < n; s += TEAM) {
-    s_open[s] = s == 0 ? 0 : op[s];
-    s_close[s] = s == 0 ? kUnbounded : cl[s];
-    s_sv[s] = s == 0 ? 0 : sv[s];
-    s_qd[s] = s == 0 ? 0 : quantize_mm(dem[s]);
-    const int p = s == 0 ? -1 : pf[s];
-    const bool named = p >= 1 && p <= ns && p != s;
-    s_kind[s] = named ? kDelivery : kPlain;
-    s_mate[s] = named ? p : 0;
+  window_gather<TEAM>(row, vw, NM, n, tid, [&](int s) {
+    kind_mate_named(row.pf, s, ns, s_kind, s_mate);
     s_pos[s] = -1;
-  }
+  });
   flat_build<TEAM>(flat, s_bnd, vrow, trow, ns, tid);  // its first barrier covers the writes above
   // the pickups learn their deliveries (status 0: K6f found pickup_from well formed) and every stop
   // its flat position; only kind / mate of stops that are no delivery are written here
@@ -300,7 +253,7 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void pd_improve_kernel(
     const FlatOrder co = flat.copy(cur, V4);
     const int *ord = co.ord, *tof = co.tof, *tst = co.tst, *cnt = co.cnt;
     const int* pos = s_pos + cur * V4;
-    const PdView vw = {sQ, sT, s_open, s_close, s_sv, s_qd, s_kind, s_mate, ord, S, cap_q};
+    const PdView pv = {vw, s_kind, s_mate, ord, cap_q};
     // 0. per trip: dep, load and pm forwards, z backwards, its length and whether it is sound
     for (int x = tid; x < m; x += TEAM) {
       const int st = tst[x], c = cnt[x];
@@ -331,15 +284,7 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void pd_improve_kernel(
         }
         len += sQ[a * S];
         ok = ok && sQ[a * S] != kUnusable && sT[a * S] != kUnusable && top <= cap_q;
-        long long zz = s_close[a];
-        s_z[st + c - 1] = zz;
-        for (int y = c - 2; y >= 0; --y) {
-          const int b = ord[st + y];
-          const long long v = zz - sT[b * S + a] - s_sv[b];
-          zz = s_close[b] < v ? s_close[b] : v;
-          s_z[st + y] = zz;
-          a = b;
-        }
+        trip_z(vw, TripView{ord + st, c, s_dep + st, s_z + st});
       }
       s_Lq[x] = len;
       s_snd[x] = ok ? 1 : 0;
@@ -353,7 +298,7 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void pd_improve_kernel(
         const int A = tof[p], fb = tst[A], x = p - fb + 1;
         const int yv = kd == kPickup ? pos[s_mate[s]] - fb + 1 : 0;
         long long len;
-        const bool ok = walk_without(vw, fb, cnt[A], x, yv, 0, 0, 0, 0, 0, 0,
+        const bool ok = walk_without(pv, fb, cnt[A], x, yv, 0, 0, 0, 0, 0, 0,
                                      s_ld0[A] - (kd == kPlain ? s_qd[s] : 0), nullptr, len);
         s_rem[p] = s_Lq[A] - len;
         w = (unsigned)x | ((unsigned)yv << 8) | ((unsigned)A << 16) | ((ok && len <= max_q) ? 1u << 24 : 0u) |
@@ -499,7 +444,7 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void pd_improve_kernel(
             long long len;
             // the walk only where it can matter, and only over what changes
             if (g > 0 && (g > bg || (g == bg && code < bc)) && LB - g <= max_q &&
-                walk_without(vw, fb, kB, x, yv, u, v, i1, j1, y0, y0 == 0 ? 0 : s_dep[fb + y0 - 1],
+                walk_without(pv, fb, kB, x, yv, u, v, i1, j1, y0, y0 == 0 ? 0 : s_dep[fb + y0 - 1],
                              y0 == 0 ? s_ld0[A] : s_load[fb + y0 - 1], sound ? s_z : nullptr, len)) {
               bg = g;
               bc = code;
@@ -587,24 +532,9 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void pd_improve_kernel(
         const double* wv = s_dv + x * V8;
         const double* wm = s_dm + x * V8;
         if (c > 0 && (tid & 1) == 0) {
-          double s = 0.0;
-          for (int p = 0; p < c; ++p) s += wv[p];
-          ok = s + wv[c] <= MD ? 1 : 0;
+          ok = length_walk(wv, c, MD) ? 1 : 0;
         } else if (c > 0) {
-          double bs = 0.0;
-          for (int p = 0; p < c; ++p)
-            if (s_kind[nx.ord[st + p]] == kPlain) bs += wm[p];
-          bool fits = bs <= CAP;
-          double load = bs;
-          for (int p = 0; p < c; ++p) {
-            if (s_kind[nx.ord[st + p]] == kPickup) {
-              load += wm[p];
-              fits = fits && load <= CAP;
-            } else {
-              load -= wm[p];
-            }
-          }
-          ok = fits ? 1 : 0;
+          ok = pd_load_walk(wm, c, CAP, [&](int p) { return s_kind[nx.ord[st + p]]; }) ? 1 : 0;
         }
       }
       s_misc[tid] = ok;
@@ -645,7 +575,7 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void pd_improve_kernel(
   if (tid == 0) {
     long long after;
     const int k = flat_rank(cnt, s_Lq, m, s_rank, after);
-    ntrips[r] = k;
+    rows.ntrips[r] = k;
     srow[0] = moves;
     srow[1] = pair_moves;
     srow[2] = rejected;
@@ -655,31 +585,18 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void pd_improve_kernel(
     srow[6] = after;
   }
   Tm::sync();
-  long long wait_part = 0;
-  for (int p = tid; p < ns; p += TEAM) {
-    vrow[p] = ord[p];
-    trow[p] = s_rank[tof[p]];
-    arow[p] = s_z[p];
-    strow[p] = s_dep[p];
-    wait_part += s_dep[p] - s_z[p];
-  }
+  const long long wait_part =
+      schedule_out<TEAM>(row, 0, ord, s_z, s_dep, ns, tid, [&](int p) { return s_rank[tof[p]]; });
   const long long waiting = Tm::sum(wait_part, s_redg, tid);
   if (tid == 0) srow[7] = waiting;
 }
 
 }  // namespace
 
-hipError_t launch_pd_improve(const double* D, const double* T, const int* npts, const double* demand,
-                             const double* cap, const double* maxd, const long long* open,
-                             const long long* close, const long long* service, const int* pickup_from,
-                             const unsigned char* flag, int R, int NM, int* visit, int* trip_of, int* ntrips,
-                             const int* status, long long* arrival, long long* start, long long* stats,
-                             hipStream_t stream) {
+hipError_t launch_pd_improve(const WindowedRows& rows, hipStream_t stream) {
   // both int32 matrices of 128 stops (2 x 66.6 KB) and the per-stop / per-position / per-trip arrays
-  return team::launch_two_tiers<PdImproveLds>(pd_improve_kernel<64>, pd_improve_kernel<team::kLargeTeam>, R, NM,
-                                              stream, D, T, npts, demand, cap, maxd, open, close, service,
-                                              pickup_from, flag, R, NM, visit, trip_of, ntrips, status, arrival,
-                                              start, stats);
+  return team::launch_two_tiers<PdImproveLds>(pd_improve_kernel<64>, pd_improve_kernel<team::kLargeTeam>, rows.R,
+                                              rows.NM, stream, rows);
 }
 
 }  // namespace rt

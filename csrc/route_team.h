@@ -32,7 +32,7 @@ constexpr int kMaxStops = 128;
 constexpr int kSmallStops = 32;
 constexpr int kLargeTeam = 1024;
 
-// The quantizers are bit-identical to routest_amd/routing/*.py and runtime/route_core.h.
+// The quantizers are bit-identical to routest_amd/routing/*.py and runtime/route_trips.h.
 __device__ __forceinline__ long long quantize_mm(double x) {
   if (!(x >= 0.0) || x >= 1099511627776.0) return kBig;  // NaN, +-inf, negatives, >= 2^40
   return __double2ll_rn(x * 1000.0);

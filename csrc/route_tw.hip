@@ -4,10 +4,12 @@
 // The definition (fixed-point millimetres and milliseconds, the unusable-entry rule, the schedule
 // and latest-start recurrences, alone-feasibility, the seed rule, the O(1) admissibility test, the
 // (ins, u, j) tie rule and the f64 acceptance walks) is in routest_amd/routing/timewindows.py; the
-// host C++ is rtr::tw_trips (runtime/route_core.h).  All three are compared with ==: every quantity
+// host C++ is rtr::tw_trips (runtime/route_trips.h).  All three are compared with ==: every quantity
 // the search orders by is an int64 sum, so the schedule below cannot change it.
 //
-// One TEAM of threads per request row (teams, tiers and the barrier discipline: route_team.h).
+// One TEAM of threads per request row (teams, tiers and the barrier discipline: route_team.h).  What
+// K6d shares with K6e-K6g (the launch arguments, the LDS prefix, the gather, the walks over one trip
+// and the f64 length walk) is in route_windows.h.
 //
 // The row's two quantized matrices are gathered ONCE into LDS as int32 (an unusable entry is
 // INT_MAX, so the narrowing is exact), with open / close / service / demand (int64), the trip
@@ -21,8 +23,7 @@
 //      one per walk, add them in order (the only place where float association matters);
 //   4. accepted: the order shifts by one position per thread, one lane recomputes dep, one z.
 // A closed trip's stops, arrivals and starts go out one position per thread.
-#include "ops.h"
-#include "route_team.h"
+#include "route_windows.h"
 
 namespace rt {
 
@@ -32,18 +33,11 @@ using namespace team;
 
 // LDS of one team (offsets in bytes), for a stop capacity of kc
 struct TwLds {
-  size_t Q = 0, T = 0, open = 0, close = 0, sv = 0, qd = 0, dep = 0, z = 0, dv = 0, dm = 0, ord = 0, unr = 0,
-         reda = 0, redb = 0, misc = 0, bytes = 0;
+  WindowLds w;
+  size_t dv = 0, dm = 0, ord = 0, unr = 0, reda = 0, redb = 0, misc = 0, bytes = 0;
   __host__ __device__ constexpr explicit TwLds(int kc) {
     LdsCarve c;
-    Q = c.take(4, (size_t)(kc + 1) * matrix_stride(kc));
-    T = c.take(4, (size_t)(kc + 1) * matrix_stride(kc));
-    open = c.take(8, kc + 4);
-    close = c.take(8, kc + 4);
-    sv = c.take(8, kc + 4);
-    qd = c.take(8, kc + 4);
-    dep = c.take(8, kc + 4);  // [0..k]
-    z = c.take(8, kc + 4);    // [1..k]
+    w = WindowLds(c, kc);
     dv = c.take(8, kc + 4);   // the lengthened trip's legs, [0..k+1]
     dm = c.take(8, kc + 4);   // ... and its stops' demands, [0..k]
     ord = c.take(4, kc + 4);  // the trip 0, s1..sk, 0: [0..k+1]
@@ -59,271 +53,210 @@ static_assert(TwLds(32).bytes == 11616 && TwLds(128).bytes == 142944, "the layou
 // KC: stop capacity of the LDS carve (the launch sizes the dynamic region for it).  It must stay the
 // first parameter: launch_two_tiers passes it there, in front of the launch's own arguments.
 template <int TEAM>
-__global__ __launch_bounds__(Team<TEAM>::BLOCK) void tw_trips_kernel(
-    int KC, const double* __restrict__ D, const double* __restrict__ T, const int* __restrict__ npts,
-    const double* __restrict__ demand, const double* __restrict__ cap, const double* __restrict__ maxd,
-    const long long* __restrict__ open, const long long* __restrict__ close,
-    const long long* __restrict__ service, const unsigned char* __restrict__ flag, int R, int NM,
-    int* __restrict__ visit, int* __restrict__ trip_of, int* __restrict__ ntrips, int* __restrict__ status,
-    long long* __restrict__ arrival, long long* __restrict__ start, long long* __restrict__ stats) {
+__global__ __launch_bounds__(Team<TEAM>::BLOCK) void tw_trips_kernel(int KC, const WindowedRows rows) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   using Tm = Team<TEAM>;
-  const Row rw = Tm::row(npts, R, NM);
+  const Row rw = Tm::row(rows.npts, rows.R, rows.NM);
   if (!rw.mine) return;
-  const int tid = rw.tid, r = rw.r, n = rw.n, ns = rw.ns;
-  if (flag[r] == 0) return;  // not a time-window row: nothing of it is touched
-  long long* srow = stats + (size_t)r * 4;  // insertions, rejected, len_q, waiting_q
-  if (ns == 0 || ns > kMaxStops || ns > KC) {
-    if (tid == 0) {
-      ntrips[r] = 0;
-      status[r] = ns == 0 ? 0 : 2;  // 2: more stops than the stage takes
-      srow[0] = srow[1] = srow[2] = srow[3] = 0;
-    }
-    return;
-  }
-
-  const TwLds L(KC);
-  unsigned char* base = smem + (size_t)rw.team * L.bytes;
-  const int S = matrix_stride(KC);
-  int* sQ = (int*)(base + L.Q);
-  int* sT = (int*)(base + L.T);
-  long long* s_open = (long long*)(base + L.open);
-  long long* s_close = (long long*)(base + L.close);
-  long long* s_sv = (long long*)(base + L.sv);
-  long long* s_qd = (long long*)(base + L.qd);
-  long long* s_dep = (long long*)(base + L.dep);
-  long long* s_z = (long long*)(base + L.z);
-  double* s_dv = (double*)(base + L.dv);
-  double* s_dm = (double*)(base + L.dm);
-  int* s_ord = (int*)(base + L.ord);
-  int* s_unr = (int*)(base + L.unr);
-  long long* s_reda = (long long*)(base + L.reda);
-  long long* s_redb = (long long*)(base + L.redb);
-  int* s_misc = (int*)(base + L.misc);
-
-  const double* d = D + (size_t)r * NM * NM;
-  const double* t = T + (size_t)r * NM * NM;
-  const double* dem = demand + (size_t)r * NM;
-  const long long* op = open + (size_t)r * NM;
-  const long long* cl = close + (size_t)r * NM;
-  const long long* sv = service + (size_t)r * NM;
-  int* vrow = visit + (size_t)r * NM;
-  int* trow = trip_of + (size_t)r * NM;
-  long long* arow = arrival + (size_t)r * NM;
-  long long* strow = start + (size_t)r * NM;
-  const double MD = maxd[r], CAP = cap[r];
-  const long long cap_q = quantize_limit(CAP), max_q = quantize_limit(MD);
-
-  // ---- gather: both quantized matrices and the per-stop vectors
-  for (int c = tid; c < n * n; c += TEAM) {
-    const int a = c / n, b = c - a * n;
-    sQ[a * S + b] = quantize_entry(d[(size_t)a * NM + b]);
-    sT[a * S + b] = quantize_entry(t[(size_t)a * NM + b]);
-  }
-  for (int s = tid; s < n; s += TEAM) {
-    s_open[s] = s == 0 ? 0 : op[s];
-    s_close[s] = s == 0 ? kUnbounded : cl[s];
-    s_sv[s] = s == 0 ? 0 : sv[s];
-    s_qd[s] = s == 0 ? 0 : quantize_mm(dem[s]);
-  }
-  Tm::sync();
-
-  // ---- alone-feasibility of every stop
-  long long nbad = 0;
-  for (int s = 1 + tid; s <= ns; s += TEAM) {
-    bool ok = dem[s] <= CAP && (0.0 + (d[s] + d[(size_t)s * NM])) <= MD;
-    const int t0s = sT[s], ts0 = sT[s * S];
-    ok = ok && sQ[s] != kUnusable && sQ[s * S] != kUnusable && t0s != kUnusable && ts0 != kUnusable;
-    const long long st0 = (long long)t0s > s_open[s] ? (long long)t0s : s_open[s];
-    ok = ok && st0 <= s_close[s];
-    s_unr[s] = ok ? 0 : 1;
-    nbad += ok ? 0 : 1;
-  }
-  nbad = Tm::sum(nbad, s_reda, tid);
-  Tm::sync();
-  if (nbad != 0) {  // status 1: visit lists the stops that passed, so the others are the failing ones
-    if (tid == 0) {
-      int k = 0;
-      for (int s = 1; s <= ns; ++s)
-        if (!s_unr[s]) vrow[k++] = s;
-      ntrips[r] = 0;
-      status[r] = 1;
-      srow[0] = srow[1] = srow[2] = srow[3] = 0;
-    }
-    return;
-  }
-  for (int s = tid; s <= ns; s += TEAM) s_unr[s] = s == 0 ? 0 : 1;
-
-  // ---- the construction
-  int left = ns, placed = 0, trips = 0;
-  long long insertions = 0, rejected = 0, len_q = 0, wait_part = 0;
-  while (left > 0) {
-    Tm::sync();
-    // the seed: the unrouted stop of smallest (close, index)
-    long long ka = LLONG_MAX, kb = LLONG_MAX;
-    for (int s = 1 + tid; s <= ns; s += TEAM)
-      if (s_unr[s]) {
-        const long long c = s_close[s];
-        if (c < ka || (c == ka && s < kb)) {
-          ka = c;
-          kb = s;
-        }
+  const int tid = rw.tid, r = rw.r, n = rw.n, ns = rw.ns, NM = rows.NM;
+  if (rows.flag[r] == 0) return;  // not a time-window row: nothing of it is touched
+  window_row_restrict(rows, r, [&](const WindowRow& row) {
+    int *ntrips = row.ntrips, *status = row.status;
+    long long* srow = row.stats + (size_t)r * 4;  // insertions, rejected, len_q, waiting_q
+    if (ns == 0 || ns > kMaxStops || ns > KC) {
+      if (tid == 0) {
+        ntrips[r] = 0;
+        status[r] = ns == 0 ? 0 : 2;  // 2: more stops than the stage takes
+        srow[0] = srow[1] = srow[2] = srow[3] = 0;
       }
-    Tm::min2(ka, kb, s_reda, s_redb, tid);
-    if (kb == LLONG_MAX) break;  // cannot happen: left > 0 stops are unrouted (uniform over the team)
-    const int seed = (int)kb;    // 1..ns
-    int k = 1;
-    long long Lq = (long long)sQ[seed] + sQ[seed * S], Wq = s_qd[seed];
-    if (tid == 0) {
-      s_ord[0] = 0;
-      s_ord[1] = seed;
-      s_ord[2] = 0;
-      s_unr[seed] = 0;
+      return;
     }
-    --left;
+
+    const TwLds L(KC);
+    unsigned char* base = smem + (size_t)rw.team * L.bytes;
+    const WindowView vw = window_view(base, L.w, KC);
+    const int S = vw.S;
+    int *sQ = vw.sQ, *sT = vw.sT;
+    long long *s_open = vw.open, *s_close = vw.close, *s_sv = vw.sv, *s_qd = vw.qd, *s_dep = vw.dep, *s_z = vw.z;
+    double* s_dv = (double*)(base + L.dv);
+    double* s_dm = (double*)(base + L.dm);
+    int* s_ord = (int*)(base + L.ord);
+    int* s_unr = (int*)(base + L.unr);
+    long long* s_reda = (long long*)(base + L.reda);
+    long long* s_redb = (long long*)(base + L.redb);
+    int* s_misc = (int*)(base + L.misc);
+
+    const double *d = row.d, *dem = row.dem;
+    int* vrow = row.vrow;
+    const double MD = row.MD, CAP = row.CAP;
+    const long long cap_q = row.cap_q, max_q = row.max_q;
+
+    // ---- gather: both quantized matrices and the per-stop vectors
+    window_gather<TEAM>(row, vw, NM, n, tid, [](int) {});
+    Tm::sync();
+
+    // ---- alone-feasibility of every stop
+    long long nbad = 0;
+    for (int s = 1 + tid; s <= ns; s += TEAM) {
+      bool ok = dem[s] <= CAP && (0.0 + (d[s] + d[(size_t)s * NM])) <= MD;
+      const int t0s = sT[s], ts0 = sT[s * S];
+      ok = ok && sQ[s] != kUnusable && sQ[s * S] != kUnusable && t0s != kUnusable && ts0 != kUnusable;
+      const long long st0 = (long long)t0s > s_open[s] ? (long long)t0s : s_open[s];
+      ok = ok && st0 <= s_close[s];
+      s_unr[s] = ok ? 0 : 1;
+      nbad += ok ? 0 : 1;
+    }
+    nbad = Tm::sum(nbad, s_reda, tid);
+    Tm::sync();
+    if (nbad != 0) {  // status 1: visit lists the stops that passed, so the others are the failing ones
+      if (tid == 0) {
+        int k = 0;
+        for (int s = 1; s <= ns; ++s)
+          if (!s_unr[s]) vrow[k++] = s;
+        ntrips[r] = 0;
+        status[r] = 1;
+        srow[0] = srow[1] = srow[2] = srow[3] = 0;
+      }
+      return;
+    }
+    for (int s = tid; s <= ns; s += TEAM) s_unr[s] = s == 0 ? 0 : 1;
+
+    // ---- the construction
+    int left = ns, placed = 0, trips = 0;
+    long long insertions = 0, rejected = 0, len_q = 0, wait_part = 0;
     while (left > 0) {
       Tm::sync();
-      // dep[0..k] and z[1..k] of the trip as it stands, one lane each
-      if (tid == 0) {
-        long long dp = 0;
-        s_dep[0] = 0;
-        for (int i = 1; i <= k; ++i) {
-          const int a = s_ord[i - 1], b = s_ord[i];
-          const long long ar = dp + sT[a * S + b];
-          dp = (ar > s_open[b] ? ar : s_open[b]) + s_sv[b];
-          s_dep[i] = dp;
-        }
-      } else if (tid == 1) {
-        long long zz = s_close[s_ord[k]];
-        s_z[k] = zz;
-        for (int i = k - 1; i >= 1; --i) {
-          const int a = s_ord[i], b = s_ord[i + 1];
-          const long long v = zz - sT[a * S + b] - s_sv[a];
-          zz = s_close[a] < v ? s_close[a] : v;
-          s_z[i] = zz;
-        }
-      }
-      Tm::sync();
-
-      // 1. the candidate scan: this lane's position j, the unrouted stops u it strides over
-      const Lanes ln = Tm::split(k + 1, tid);
-      const int CW = ln.CW, col0 = ln.col0, row0 = ln.row0, rstep = ln.rstep;
-      long long bi = LLONG_MAX, bc = LLONG_MAX;
-      for (int j = col0; j <= k; j += CW) {
-        const int a = s_ord[j], b = s_ord[j + 1];
-        const long long depj = s_dep[j], qab = sQ[a * S + b];
-        const long long zn = j < k ? s_z[j + 1] : 0;
-        const int* qa = sQ + a * S;
-        const int* ta = sT + a * S;
-        for (int u = 1 + row0; u <= ns; u += rstep) {
-          if (!s_unr[u]) continue;
-          const int qau = qa[u], qub = sQ[u * S + b], tau = ta[u], tub = sT[u * S + b];
-          if (qau == kUnusable || qub == kUnusable || tau == kUnusable || tub == kUnusable) continue;
-          const long long ins = (long long)qau + qub - qab;
-          const long long ar = depj + tau;
-          const long long st = ar > s_open[u] ? ar : s_open[u];
-          if (st > s_close[u]) continue;
-          if (j < k && st + s_sv[u] + tub > zn) continue;
-          if (!(Wq + s_qd[u] <= cap_q) || !(Lq + ins <= max_q)) continue;
-          const long long code = ((long long)u << 8) | j;
-          if (ins < bi || (ins == bi && code < bc)) {
-            bi = ins;
-            bc = code;
+      // the seed: the unrouted stop of smallest (close, index)
+      long long ka = LLONG_MAX, kb = LLONG_MAX;
+      for (int s = 1 + tid; s <= ns; s += TEAM)
+        if (s_unr[s]) {
+          const long long c = s_close[s];
+          if (c < ka || (c == ka && s < kb)) {
+            ka = c;
+            kb = s;
           }
         }
-      }
-      // 2. (min ins, then min code) over the team
-      Tm::min2(bi, bc, s_reda, s_redb, tid);
-      if (bc == LLONG_MAX) break;  // no admissible candidate: the trip is closed
-      const int bu = (int)(bc >> 8), bj = (int)(bc & 255);
-
-      // 3. acceptance as the greedy measures it: the lengthened trip, f64, in visiting order
-      const int kk = k + 1;  // its stops; position p of it is ord[p], u at bj + 1, ord[p - 1] behind
-      for (int e = tid; e <= kk; e += TEAM) {
-        const int a = e <= bj ? s_ord[e] : (e == bj + 1 ? bu : s_ord[e - 1]);
-        const int b = e + 1 <= bj ? s_ord[e + 1] : (e == bj ? bu : s_ord[e]);
-        s_dv[e] = d[(size_t)a * NM + b];
-        if (e < kk) s_dm[e] = dem[b];
-      }
-      Tm::sync();
+      Tm::min2(ka, kb, s_reda, s_redb, tid);
+      if (kb == LLONG_MAX) break;  // cannot happen: left > 0 stops are unrouted (uniform over the team)
+      const int seed = (int)kb;    // 1..ns
+      int k = 1;
+      long long Lq = (long long)sQ[seed] + sQ[seed * S], Wq = s_qd[seed];
       if (tid == 0) {
-        double s = 0.0;
-        for (int p = 0; p < kk; ++p) s += s_dv[p];
-        s_misc[0] = s + s_dv[kk] <= MD ? 1 : 0;
-      } else if (tid == 1) {
-        double load = 0.0;
-        for (int p = 0; p < kk; ++p) load += s_dm[p];
-        s_misc[1] = load <= CAP ? 1 : 0;
+        s_ord[0] = 0;
+        s_ord[1] = seed;
+        s_ord[2] = 0;
+        s_unr[seed] = 0;
       }
-      Tm::sync();
-      if (!(s_misc[0] != 0 && s_misc[1] != 0)) {  // not applied: the trip is closed
-        ++rejected;
-        break;
-      }
-
-      // 4. the insertion: the positions behind bj move back by one, one position per thread
-      const int p = tid;  // k + 3 <= TEAM positions in both tiers
-      const int moved = (p >= bj + 2 && p <= kk + 1) ? s_ord[p - 1] : 0;
-      Tm::sync();
-      if (p >= bj + 2 && p <= kk + 1) s_ord[p] = moved;
-      if (p == bj + 1) {
-        s_ord[p] = bu;
-        s_unr[bu] = 0;
-      }
-      k = kk;
-      Lq += bi;
-      Wq += s_qd[bu];
-      ++insertions;
       --left;
-    }
-    Tm::sync();
-    // the closed trip: one lane walks its schedule (arrivals into z[], starts into dep[], both no
-    // longer needed), then its stops, arrivals and starts go out one position per thread
-    if (tid == 0) {
-      long long dp = 0;
-      for (int i = 1; i <= k; ++i) {
-        const int a = s_ord[i - 1], b = s_ord[i];
-        const long long ar = dp + sT[a * S + b];
-        const long long stt = ar > s_open[b] ? ar : s_open[b];
-        s_z[i] = ar;
-        s_dep[i] = stt;
-        dp = stt + s_sv[b];
+      while (left > 0) {
+        Tm::sync();
+        // dep[0..k] and z[1..k] of the trip as it stands, one lane each
+        const TripView trip = {s_ord + 1, k, s_dep + 1, s_z + 1};
+        if (tid == 0) {
+          s_dep[0] = 0;
+          trip_dep(vw, trip);
+        } else if (tid == 1) {
+          trip_z(vw, trip);
+        }
+        Tm::sync();
+
+        // 1. the candidate scan: this lane's position j, the unrouted stops u it strides over
+        const Lanes ln = Tm::split(k + 1, tid);
+        const int CW = ln.CW, col0 = ln.col0, row0 = ln.row0, rstep = ln.rstep;
+        long long bi = LLONG_MAX, bc = LLONG_MAX;
+        for (int j = col0; j <= k; j += CW) {
+          const int a = s_ord[j], b = s_ord[j + 1];
+          const long long depj = s_dep[j], qab = sQ[a * S + b];
+          const long long zn = j < k ? s_z[j + 1] : 0;
+          const int* qa = sQ + a * S;
+          const int* ta = sT + a * S;
+          for (int u = 1 + row0; u <= ns; u += rstep) {
+            if (!s_unr[u]) continue;
+            const int qau = qa[u], qub = sQ[u * S + b], tau = ta[u], tub = sT[u * S + b];
+            if (qau == kUnusable || qub == kUnusable || tau == kUnusable || tub == kUnusable) continue;
+            const long long ins = (long long)qau + qub - qab;
+            const long long ar = depj + tau;
+            const long long st = ar > s_open[u] ? ar : s_open[u];
+            if (st > s_close[u]) continue;
+            if (j < k && st + s_sv[u] + tub > zn) continue;
+            if (!(Wq + s_qd[u] <= cap_q) || !(Lq + ins <= max_q)) continue;
+            const long long code = ((long long)u << 8) | j;
+            if (ins < bi || (ins == bi && code < bc)) {
+              bi = ins;
+              bc = code;
+            }
+          }
+        }
+        // 2. (min ins, then min code) over the team
+        Tm::min2(bi, bc, s_reda, s_redb, tid);
+        if (bc == LLONG_MAX) break;  // no admissible candidate: the trip is closed
+        const int bu = (int)(bc >> 8), bj = (int)(bc & 255);
+
+        // 3. acceptance as the greedy measures it: the lengthened trip, f64, in visiting order
+        const int kk = k + 1;  // its stops; position p of it is ord[p], u at bj + 1, ord[p - 1] behind
+        for (int e = tid; e <= kk; e += TEAM) {
+          const int a = e <= bj ? s_ord[e] : (e == bj + 1 ? bu : s_ord[e - 1]);
+          const int b = e + 1 <= bj ? s_ord[e + 1] : (e == bj ? bu : s_ord[e]);
+          s_dv[e] = d[(size_t)a * NM + b];
+          if (e < kk) s_dm[e] = dem[b];
+        }
+        Tm::sync();
+        if (tid == 0) {
+          s_misc[0] = length_walk(s_dv, kk, MD) ? 1 : 0;
+        } else if (tid == 1) {
+          double load = 0.0;
+          for (int p = 0; p < kk; ++p) load += s_dm[p];
+          s_misc[1] = load <= CAP ? 1 : 0;
+        }
+        Tm::sync();
+        if (!(s_misc[0] != 0 && s_misc[1] != 0)) {  // not applied: the trip is closed
+          ++rejected;
+          break;
+        }
+
+        // 4. the insertion: the positions behind bj move back by one, one position per thread
+        const int p = tid;  // k + 3 <= TEAM positions in both tiers
+        const int moved = (p >= bj + 2 && p <= kk + 1) ? s_ord[p - 1] : 0;
+        Tm::sync();
+        if (p >= bj + 2 && p <= kk + 1) s_ord[p] = moved;
+        if (p == bj + 1) {
+          s_ord[p] = bu;
+          s_unr[bu] = 0;
+        }
+        k = kk;
+        Lq += bi;
+        Wq += s_qd[bu];
+        ++insertions;
+        --left;
       }
+      Tm::sync();
+      // the closed trip: one lane walks its schedule (arrivals into z[], starts into dep[], both no
+      // longer needed), then its stops, arrivals and starts go out one position per thread
+      if (tid == 0) trip_schedule(vw, TripView{s_ord + 1, k, s_dep + 1, s_z + 1});
+      Tm::sync();
+      wait_part += schedule_out<TEAM>(row, placed, s_ord + 1, s_z + 1, s_dep + 1, k, tid, [&](int) { return trips; });
+      placed += k;
+      len_q += Lq;
+      ++trips;
     }
-    Tm::sync();
-    for (int i = 1 + tid; i <= k; i += TEAM) {
-      vrow[placed + i - 1] = s_ord[i];
-      trow[placed + i - 1] = trips;
-      arow[placed + i - 1] = s_z[i];
-      strow[placed + i - 1] = s_dep[i];
-      wait_part += s_dep[i] - s_z[i];
+    const long long waiting = Tm::sum(wait_part, s_reda, tid);
+    if (tid == 0) {
+      ntrips[r] = trips;
+      status[r] = 0;
+      srow[0] = insertions;
+      srow[1] = rejected;
+      srow[2] = len_q;
+      srow[3] = waiting;
     }
-    placed += k;
-    len_q += Lq;
-    ++trips;
-  }
-  const long long waiting = Tm::sum(wait_part, s_reda, tid);
-  if (tid == 0) {
-    ntrips[r] = trips;
-    status[r] = 0;
-    srow[0] = insertions;
-    srow[1] = rejected;
-    srow[2] = len_q;
-    srow[3] = waiting;
-  }
+  });
 }
 
 }  // namespace
 
-hipError_t launch_tw_trips(const double* D, const double* T, const int* npts, const double* demand,
-                           const double* cap, const double* maxd, const long long* open,
-                           const long long* close, const long long* service, const unsigned char* flag,
-                           int R, int NM, int* visit, int* trip_of, int* ntrips, int* status,
-                           long long* arrival, long long* start, long long* stats, hipStream_t stream) {
+hipError_t launch_tw_trips(const WindowedRows& rows, hipStream_t stream) {
   // both int32 matrices of 128 stops (2 x 66.6 KB) and the per-stop arrays
-  return team::launch_two_tiers<TwLds>(tw_trips_kernel<64>, tw_trips_kernel<team::kLargeTeam>, R, NM, stream, D,
-                                       T, npts, demand, cap, maxd, open, close, service, flag, R, NM, visit,
-                                       trip_of, ntrips, status, arrival, start, stats);
+  return team::launch_two_tiers<TwLds>(tw_trips_kernel<64>, tw_trips_kernel<team::kLargeTeam>, rows.R, rows.NM,
+                                       stream, rows);
 }
 
 }  // namespace rt

@@ -4,11 +4,13 @@
 // The definition (fixed-point millimetres and milliseconds, the unusable-entry rule, the three move
 // types with their limits and O(1) / bounded-walk time tests, best-improvement selection with the
 // (type, A, i, B, j) tie rule, the f64 acceptance walks, the move cap and the skip conditions) is in
-// routest_amd/routing/tw_improve.py; the host C++ is rtr::tw_improve_trips (runtime/route_core.h).
+// routest_amd/routing/tw_improve.py; the host C++ is rtr::tw_improve_trips (runtime/route_trips.h).
 // All three are compared with ==: every quantity the search orders by is an int64 sum, so the
 // schedule below cannot change it.
 //
-// One TEAM of threads per request row (teams, tiers and the barrier discipline: route_team.h).
+// One TEAM of threads per request row (teams, tiers and the barrier discipline: route_team.h).  What
+// K6e shares with K6d, K6f and K6g (the launch arguments, the LDS prefix, the gather, the row as the
+// constructor left it and the walks over one trip) is in route_windows.h.
 //
 // The row's two quantized matrices are gathered ONCE into LDS as int32 (an unusable entry is
 // INT_MAX, so the narrowing is exact), as K6d does, with open / close / service / demand (int64).
@@ -32,8 +34,7 @@
 //      rejected: the first copy stays and the search ends.
 // At the end the non-empty trips are compacted: one lane per trip walks its schedule, the positions
 // go out one per thread and the waiting time by a team sum.
-#include "ops.h"
-#include "route_team.h"
+#include "route_windows.h"
 
 namespace rt {
 
@@ -43,20 +44,13 @@ using namespace team;
 
 // LDS of one team (offsets in bytes), for a stop capacity of kc; [2]: two arrays of stride v8 / v4
 struct TwImproveLds {
-  size_t Q = 0, T = 0, open = 0, close = 0, sv = 0, qd = 0, dep = 0, z = 0, Lq = 0, Wq = 0, rem = 0, nb = 0,
-         dv = 0, dm = 0, ord = 0, tof = 0, tst = 0, cnt = 0, pw = 0, pn = 0, rank = 0, bnd = 0, redg = 0,
-         redc = 0, misc = 0, bytes = 0;
+  WindowLds w;  // dep, z: per flat position, the departure and the latest start of its stop
+  size_t Lq = 0, Wq = 0, rem = 0, nb = 0, dv = 0, dm = 0, ord = 0, tof = 0, tst = 0, cnt = 0, pw = 0, pn = 0,
+         rank = 0, bnd = 0, redg = 0, redc = 0, misc = 0, bytes = 0;
   int v8 = 0, v4 = 0;
   __host__ __device__ constexpr explicit TwImproveLds(int kc) {
     LdsCarve c;
-    Q = c.take(4, (size_t)(kc + 1) * matrix_stride(kc));
-    T = c.take(4, (size_t)(kc + 1) * matrix_stride(kc));
-    open = c.take(8, kc + 4);
-    close = c.take(8, kc + 4);
-    sv = c.take(8, kc + 4);
-    qd = c.take(8, kc + 4);
-    dep = c.take(8, kc + 4);    // per flat position: the departure of its stop
-    z = c.take(8, kc + 4);      // per flat position: the latest start of its stop
+    w = WindowLds(c, kc);
     Lq = c.take(8, kc + 4);     // per trip
     Wq = c.take(8, kc + 4);
     rem = c.take(8, kc + 4);    // per flat position
@@ -84,33 +78,21 @@ static_assert(TwImproveLds(32).bytes == 14784 && TwImproveLds(128).bytes == 1545
 // KC: stop capacity of the LDS carve (the launch sizes the dynamic region for it).  It must stay the
 // first parameter: launch_two_tiers passes it there, in front of the launch's own arguments.
 template <int TEAM>
-__global__ __launch_bounds__(Team<TEAM>::BLOCK) void tw_improve_kernel(
-    int KC, const double* __restrict__ D, const double* __restrict__ T, const int* __restrict__ npts,
-    const double* __restrict__ demand, const double* __restrict__ cap, const double* __restrict__ maxd,
-    const long long* __restrict__ open, const long long* __restrict__ close,
-    const long long* __restrict__ service, const unsigned char* __restrict__ flag, int R, int NM,
-    int* __restrict__ visit, int* __restrict__ trip_of, int* __restrict__ ntrips,
-    const int* __restrict__ status, long long* __restrict__ arrival, long long* __restrict__ start,
-    long long* __restrict__ stats) {
+__global__ __launch_bounds__(Team<TEAM>::BLOCK) void tw_improve_kernel(int KC, const WindowedRows rows) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   using Tm = Team<TEAM>;
-  const Row rw = Tm::row(npts, R, NM);
+  const Row rw = Tm::row(rows.npts, rows.R, rows.NM);
   if (!rw.mine) return;
-  const int tid = rw.tid, r = rw.r, n = rw.n, ns = rw.ns;
-  if (flag[r] == 0 || status[r] != 0) return;  // not asked for, or not planned: nothing is touched
+  const int tid = rw.tid, r = rw.r, n = rw.n, ns = rw.ns, NM = rows.NM;
+  if (rows.flag[r] == 0 || rows.status[r] != 0) return;  // not asked for, or not planned: nothing is touched
   if (ns == 0 || ns > kMaxStops || ns > KC) return;
 
   const TwImproveLds L(KC);
   unsigned char* base = smem + (size_t)rw.team * L.bytes;
-  const int S = matrix_stride(KC), V4 = L.v4, V8 = L.v8;
-  int* sQ = (int*)(base + L.Q);
-  int* sT = (int*)(base + L.T);
-  long long* s_open = (long long*)(base + L.open);
-  long long* s_close = (long long*)(base + L.close);
-  long long* s_sv = (long long*)(base + L.sv);
-  long long* s_qd = (long long*)(base + L.qd);
-  long long* s_dep = (long long*)(base + L.dep);
-  long long* s_z = (long long*)(base + L.z);
+  const WindowView vw = window_view(base, L.w, KC);
+  const int S = vw.S, V4 = L.v4, V8 = L.v8;
+  int *sQ = vw.sQ, *sT = vw.sT;
+  long long *s_open = vw.open, *s_close = vw.close, *s_sv = vw.sv, *s_qd = vw.qd, *s_dep = vw.dep, *s_z = vw.z;
   long long* s_Lq = (long long*)(base + L.Lq);
   long long* s_Wq = (long long*)(base + L.Wq);
   long long* s_rem = (long long*)(base + L.rem);
@@ -127,47 +109,21 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void tw_improve_kernel(
   long long* s_redc = (long long*)(base + L.redc);
   int* s_misc = (int*)(base + L.misc);
 
-  const double* d = D + (size_t)r * NM * NM;
-  const double* t = T + (size_t)r * NM * NM;
-  const double* dem = demand + (size_t)r * NM;
-  const long long* op = open + (size_t)r * NM;
-  const long long* cl = close + (size_t)r * NM;
-  const long long* sv = service + (size_t)r * NM;
-  int* vrow = visit + (size_t)r * NM;
-  int* trow = trip_of + (size_t)r * NM;
-  long long* arow = arrival + (size_t)r * NM;
-  long long* strow = start + (size_t)r * NM;
-  long long* srow = stats + (size_t)r * 7;
-  const double MD = maxd[r], CAP = cap[r];
-  const long long cap_q = quantize_limit(CAP), max_q = quantize_limit(MD);
+  const WindowRow row = window_row(rows, r);
+  const double *d = row.d, *dem = row.dem;
+  int *vrow = row.vrow, *trow = row.trow;
+  long long* srow = rows.stats + (size_t)r * 7;
+  const double MD = row.MD, CAP = row.CAP;
+  const long long cap_q = row.cap_q, max_q = row.max_q;
 
   // ---- the row as K6d left it, from global memory: its trips, its waiting time, its validity
-  long long groups = 0, wait0 = 0, badv = 0;
-  for (int p = tid; p < ns; p += TEAM) {
-    const int v = vrow[p];
-    badv += (v < 1 || v >= n) ? 1 : 0;
-    groups += (p == 0 || trow[p] != trow[p - 1]) ? 1 : 0;
-    wait0 += strow[p] - arow[p];
-  }
-  const int m = (int)Tm::sum(groups, s_redg, tid);
-  wait0 = Tm::sum(wait0, s_redg, tid);
-  if (Tm::sum(badv, s_redg, tid) != 0) return;  // not K6d's output: leave the row alone
+  int m;
+  long long wait0;
+  if (!left_by_constructor<TEAM>(row, n, ns, s_redg, tid, m, wait0)) return;  // not K6d's output
 
   // ---- gather: both quantized matrices, the per-stop vectors, the order, the trips
-  for (int c = tid; c < n * n; c += TEAM) {
-    const int a = c / n, b = c - a * n;
-    sQ[a * S + b] = quantize_entry(d[(size_t)a * NM + b]);
-    sT[a * S + b] = quantize_entry(t[(size_t)a * NM + b]);
-  }
   long long bigdem = 0;
-  for (int s = tid; s < n; s += TEAM) {
-    s_open[s] = s == 0 ? 0 : op[s];
-    s_close[s] = s == 0 ? kUnbounded : cl[s];
-    s_sv[s] = s == 0 ? 0 : sv[s];
-    const long long qd = s == 0 ? 0 : quantize_mm(dem[s]);
-    s_qd[s] = qd;
-    bigdem += qd == kBig ? 1 : 0;
-  }
+  window_gather<TEAM>(row, vw, NM, n, tid, [&](int s) { bigdem += s_qd[s] == kBig ? 1 : 0; });
   flat_build<TEAM>(flat, s_bnd, vrow, trow, ns, tid);
   const long long part = flat_trip_sums<TEAM>(flat, m, sQ, S, s_qd, s_Lq, s_Wq, tid);
   const long long before = Tm::sum(part, s_redg, tid);
@@ -194,25 +150,11 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void tw_improve_kernel(
     const int *ord = co.ord, *tof = co.tof, *tst = co.tst, *cnt = co.cnt;
     // 0. dep forwards and z backwards, one lane per trip
     for (int x = tid; x < m; x += TEAM) {
-      const int st = tst[x], c = cnt[x];
-      if (c > 0) {
-        long long dp = 0;
-        int a = 0;
-        for (int y = 0; y < c; ++y) {
-          const int b = ord[st + y];
-          dp = max64(dp + sT[a * S + b], s_open[b]) + s_sv[b];
-          s_dep[st + y] = dp;
-          a = b;
-        }
-        long long zz = s_close[a];
-        s_z[st + c - 1] = zz;
-        for (int y = c - 2; y >= 0; --y) {
-          const int b = ord[st + y];
-          const long long v = zz - sT[b * S + a] - s_sv[b];
-          zz = s_close[b] < v ? s_close[b] : v;
-          s_z[st + y] = zz;
-          a = b;
-        }
+      const int st = tst[x];
+      const TripView trip = {ord + st, cnt[x], s_dep + st, s_z + st};
+      if (trip.k > 0) {
+        trip_dep(vw, trip);
+        trip_z(vw, trip);
       }
     }
     Tm::sync();
@@ -381,7 +323,7 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void tw_improve_kernel(
   if (tid == 0) {
     long long after;
     const int k = flat_rank(cnt, s_Lq, m, s_rank, after);
-    ntrips[r] = k;
+    rows.ntrips[r] = k;
     srow[0] = moves;
     srow[1] = rejected;
     srow[2] = m;
@@ -390,45 +332,21 @@ __global__ __launch_bounds__(Team<TEAM>::BLOCK) void tw_improve_kernel(
     srow[5] = after;
   }
   // one lane per trip walks its schedule: arrivals into z[], starts into dep[] (no longer needed)
-  for (int x = tid; x < m; x += TEAM) {
-    const int st = tst[x], c = cnt[x];
-    long long dp = 0;
-    int a = 0;
-    for (int y = 0; y < c; ++y) {
-      const int b = ord[st + y];
-      const long long ar = dp + sT[a * S + b];
-      const long long stt = max64(ar, s_open[b]);
-      s_z[st + y] = ar;
-      s_dep[st + y] = stt;
-      dp = stt + s_sv[b];
-      a = b;
-    }
-  }
+  for (int x = tid; x < m; x += TEAM)
+    trip_schedule(vw, TripView{ord + tst[x], cnt[x], s_dep + tst[x], s_z + tst[x]});
   Tm::sync();
-  long long wait_part = 0;
-  for (int p = tid; p < ns; p += TEAM) {
-    vrow[p] = ord[p];
-    trow[p] = s_rank[tof[p]];
-    arow[p] = s_z[p];
-    strow[p] = s_dep[p];
-    wait_part += s_dep[p] - s_z[p];
-  }
+  const long long wait_part =
+      schedule_out<TEAM>(row, 0, ord, s_z, s_dep, ns, tid, [&](int p) { return s_rank[tof[p]]; });
   const long long waiting = Tm::sum(wait_part, s_redg, tid);
   if (tid == 0) srow[6] = waiting;
 }
 
 }  // namespace
 
-hipError_t launch_tw_improve(const double* D, const double* T, const int* npts, const double* demand,
-                             const double* cap, const double* maxd, const long long* open,
-                             const long long* close, const long long* service, const unsigned char* flag,
-                             int R, int NM, int* visit, int* trip_of, int* ntrips, const int* status,
-                             long long* arrival, long long* start, long long* stats, hipStream_t stream) {
+hipError_t launch_tw_improve(const WindowedRows& rows, hipStream_t stream) {
   // both int32 matrices of 128 stops (2 x 66.6 KB) and the per-stop / per-trip arrays
-  return team::launch_two_tiers<TwImproveLds>(tw_improve_kernel<64>, tw_improve_kernel<team::kLargeTeam>, R, NM,
-                                              stream, D, T, npts, demand, cap, maxd, open, close, service,
-                                              flag, R, NM, visit, trip_of, ntrips, status, arrival, start,
-                                              stats);
+  return team::launch_two_tiers<TwImproveLds>(tw_improve_kernel<64>, tw_improve_kernel<team::kLargeTeam>, rows.R,
+                                              rows.NM, stream, rows);
 }
 
 }  // namespace rt

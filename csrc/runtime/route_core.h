@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "json_lite.h"
+#include "route_trips.h"
 #include "rt_core.h"
 
 namespace rtr {
@@ -929,20 +930,6 @@ inline std::string p2p_errors(const RouteReq& r, double dist_m) {
 }
 
 // ------------------------------------------------------------------ whole-request assembly
-// What the trip improvement did to one request (routing/improve.py improve_trips statistics).
-struct ImproveStats {
-  long long moves = 0, trips_changed = 0, len_before_q = 0, len_after_q = 0;
-  // an "exchange" request (routing/exchange.py compose_stats): `moves` sums the two intra-trip
-  // stages, the lengths span the whole pipeline, trips_changed is not reported
-  bool exchange = false;
-  long long exchange_moves = 0, trips_before = 0, trips_after = 0;
-};
-
-// What the inter-trip exchange did to one request (routing/exchange.py exchange_trips statistics).
-struct ExchangeStats {
-  long long moves = 0, rejected = 0, trips_before = 0, trips_after = 0, len_before_q = 0, len_after_q = 0;
-};
-
 // A planned request: the greedy trips (multi-stop) or the infeasible stops.
 struct Plan {
   bool infeasible = false;
@@ -1113,1093 +1100,6 @@ inline bool assemble(const RouteReq& r, const Plan& p, const std::vector<Dir>& d
   if (!put_annotation(o, r, engine)) return false;
   a.ok = true;
   return true;
-}
-
-// ------------------------------------------------------------------ CPU greedy (greedy.py)
-// Returns trips as index lists into [depot] + stops, or the infeasible stops (0-based dest idx).
-inline bool greedy_trips(const std::vector<double>& d, int n1, const std::vector<double>& dem, double cap,
-                         double maxd, std::vector<std::vector<int>>& trips, std::vector<int>& infeasible) {
-  const int n = n1 - 1;
-  std::vector<int> order(n);
-  for (int i = 0; i < n; ++i) order[i] = i + 1;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return d[a] < d[b]; });
-  std::vector<char> vis(n1, 0);
-  int remaining = n;
-  trips.clear();
-  while (remaining) {
-    std::vector<int> trip{0};
-    double load = 0.0, tdist = 0.0;
-    int cur = 0;
-    for (int idx : order) {
-      if (vis[idx]) continue;
-      const double dm = dem[idx];
-      // the reference's association: added = d[cur][idx] + d[idx][0] first, then tdist + added
-      if ((load + dm) <= cap && (tdist + (d[(size_t)cur * n1 + idx] + d[(size_t)idx * n1])) <= maxd) {
-        trip.push_back(idx);
-        load += dm;
-        tdist += d[(size_t)cur * n1 + idx];
-        cur = idx;
-      }
-    }
-    if (trip.size() == 1) {
-      infeasible.clear();
-      for (int i : order)
-        if (!vis[i]) infeasible.push_back(i - 1);
-      return false;
-    }
-    for (size_t i = 1; i < trip.size(); ++i) vis[trip[i]] = 1;
-    remaining -= (int)trip.size() - 1;
-    trip.push_back(0);
-    trips.push_back(std::move(trip));
-  }
-  return true;
-}
-
-// ------------------------------------------------------------------ trip improvement (improve.py)
-// Intra-trip best-improvement 2-opt (reversal) + Or-opt (segments of 1..3) on fixed-point
-// millimetres; the definition is in routest_amd/routing/improve.py and this follows it move for
-// move, so the two (and K6b, csrc/route_improve.hip) agree exactly.
-constexpr long long kImproveBig = 1LL << 50;
-constexpr int kImproveMaxStops = 128;
-
-inline long long improve_q(double x) {
-  if (!(x >= 0.0) || x >= 1099511627776.0) return kImproveBig;  // NaN, +-inf, negatives, >= 2^40
-  return std::llrint(x * 1000.0);                                 // round-half-even
-}
-
-// d: n1 x n1 matrix over [depot] + stops; trips as greedy_trips returns them, rewritten in place.
-inline ImproveStats improve_trips(const std::vector<double>& d, int n1, double maxd,
-                                  std::vector<std::vector<int>>& trips) {
-  ImproveStats st;
-  auto Q = [&](int a, int b) { return improve_q(d[(size_t)a * n1 + b]); };
-  std::vector<long long> P, pf, pb;
-  for (auto& trip : trips) {
-    const int k = (int)trip.size() - 2;
-    long long before = 0;
-    for (int p = 0; p + 1 < (int)trip.size(); ++p) before += Q(trip[p], trip[p + 1]);
-    st.len_before_q += before;
-    if (k < 2 || k > kImproveMaxStops) {
-      st.len_after_q += before;
-      continue;
-    }
-    // quantized sub-matrix by trip-local stop number: loc[0] = depot, loc[a] = a-th stop of the greedy
-    const int S = k + 1;
-    std::vector<int> loc(trip.begin(), trip.begin() + S);
-    P.assign((size_t)S * S, 0);
-    for (int a = 0; a < S; ++a)
-      for (int b = 0; b < S; ++b) P[(size_t)a * S + b] = Q(loc[a], loc[b]);
-    std::vector<int> t(k + 2);
-    for (int p = 0; p <= k; ++p) t[p] = p;
-    t[k + 1] = 0;
-    auto q = [&](int a, int b) { return P[(size_t)t[a] * S + t[b]]; };  // by position
-    pf.assign(k + 2, 0);
-    pb.assign(k + 2, 0);
-    long long moves = 0, after = before;
-    while (moves < 4LL * k) {
-      for (int p = 0; p <= k; ++p) {
-        pf[p + 1] = pf[p] + q(p, p + 1);
-        pb[p + 1] = pb[p] + q(p + 1, p);
-      }
-      after = pf[k + 1];
-      long long bg = 0;
-      int bt = -1, bi = -1, bj = -1;
-      for (int i = 1; i <= k; ++i)
-        for (int j = i + 1; j <= k; ++j) {
-          const long long g = (q(i - 1, i) + q(j, j + 1) + (pf[j] - pf[i])) -
-                              (q(i - 1, j) + q(i, j + 1) + (pb[j] - pb[i]));
-          if (g > bg) { bg = g; bt = 0; bi = i; bj = j; }
-        }
-      for (int len = 1; len <= 3; ++len)
-        for (int i = 1; i + len - 1 <= k; ++i) {
-          const int e = i + len - 1;
-          for (int j = 0; j <= k; ++j) {
-            if (j >= i - 1 && j <= e) continue;
-            const long long g = q(i - 1, i) + q(e, e + 1) + q(j, j + 1) - q(i - 1, e + 1) - q(j, i) - q(e, j + 1);
-            if (g > bg) { bg = g; bt = len; bi = i; bj = j; }
-          }
-        }
-      if (bg <= 0) break;
-      if (bt == 0) {
-        std::reverse(t.begin() + bi, t.begin() + bj + 1);
-      } else if (bj < bi - 1) {  // segment moves towards the front
-        std::rotate(t.begin() + bj + 1, t.begin() + bi, t.begin() + bi + bt);
-      } else {                   // towards the back
-        std::rotate(t.begin() + bi, t.begin() + bi + bt, t.begin() + bj + 1);
-      }
-      ++moves;
-      if (moves == 4LL * k) {
-        after = 0;
-        for (int p = 0; p <= k; ++p) after += q(p, p + 1);
-      }
-    }
-    bool keep = moves > 0;
-    if (keep) {  // the greedy's own f64 accumulation over the new order
-      double s = 0.0;
-      for (int p = 0; p < k; ++p) s += d[(size_t)loc[t[p]] * n1 + loc[t[p + 1]]];
-      keep = s + d[(size_t)loc[t[k]] * n1] <= maxd;
-    }
-    if (keep) {
-      for (int p = 1; p <= k; ++p) trip[p] = loc[t[p]];
-      st.moves += moves;
-      ++st.trips_changed;
-      st.len_after_q += after;
-    } else {
-      st.len_after_q += before;
-    }
-  }
-  return st;
-}
-
-// ------------------------------------------------------------------ trip exchange (exchange.py)
-// Inter-trip best-improvement relocate / swap of single stops under the capacity and the distance
-// limit, on the same fixed point; the definition is in routest_amd/routing/exchange.py and this
-// follows it move for move, so the two (and K6c, csrc/route_exchange.hip) agree exactly.
-constexpr long long kExchangeUnbounded = 1LL << 62;
-
-// cap_q / max_q: floor(x * 1000) below 2^40, unbounded from there; false for NaN and negatives
-inline bool exchange_limit(double x, long long& out) {
-  if (!(x >= 0.0)) return false;
-  out = x >= 1099511627776.0 ? kExchangeUnbounded : (long long)std::floor(x * 1000.0);
-  return true;
-}
-
-// d: n1 x n1 matrix over [depot] + stops, dem[s] per point; trips [0, ..., 0] over the stops,
-// rewritten in place (emptied trips dropped).  move_cap < 0: the default, 4 moves per stop.
-inline ExchangeStats exchange_trips(const std::vector<double>& d, int n1, const std::vector<double>& dem,
-                                    double cap, double maxd, std::vector<std::vector<int>>& trips,
-                                    long long move_cap = -1) {
-  ExchangeStats st;
-  const int ns = n1 - 1, m = (int)trips.size();
-  std::vector<long long> q((size_t)n1 * n1);
-  for (size_t x = 0; x < q.size(); ++x) q[x] = improve_q(d[x]);
-  auto Q = [&](int a, int b) { return q[(size_t)a * n1 + b]; };
-  auto length = [&](const std::vector<int>& t) {
-    long long s = 0;
-    for (size_t p = 0; p + 1 < t.size(); ++p) s += Q(t[p], t[p + 1]);
-    return s;
-  };
-  std::vector<long long> Lq(m), Wq(m, 0), qd(n1, 0);
-  int nonempty = 0;
-  for (int t = 0; t < m; ++t) {
-    Lq[t] = length(trips[t]);
-    st.len_before_q += Lq[t];
-    nonempty += trips[t].size() > 2;
-  }
-  st.len_after_q = st.len_before_q;
-  st.trips_before = st.trips_after = m;
-  bool skip = ns > kImproveMaxStops || nonempty < 2;
-  for (int s = 1; s < n1; ++s) {
-    qd[s] = improve_q(dem[s]);
-    skip = skip || qd[s] == kImproveBig;
-  }
-  long long cap_q = 0, max_q = 0;
-  if (!exchange_limit(cap, cap_q) || !exchange_limit(maxd, max_q)) skip = true;
-  if (skip) return st;
-  for (int t = 0; t < m; ++t)
-    for (size_t p = 1; p + 1 < trips[t].size(); ++p) Wq[t] += qd[trips[t][p]];
-  // the greedy's own f64 accumulations over one trip
-  auto walks = [&](const std::vector<int>& t) {
-    const int k = (int)t.size() - 2;
-    double s = 0.0, load = 0.0;
-    for (int p = 0; p < k; ++p) s += d[(size_t)t[p] * n1 + t[p + 1]];
-    for (int p = 1; p <= k; ++p) load += dem[t[p]];
-    return s + d[(size_t)t[k] * n1] <= maxd && load <= cap;
-  };
-  const long long limit = move_cap < 0 ? 4LL * ns : move_cap;
-  while (st.moves < limit) {
-    long long bg = 0;
-    int bt = -1, bA = -1, bi = -1, bB = -1, bj = -1;
-    for (int A = 0; A < m; ++A) {  // type 0: relocate a[i] to between b[j] and b[j+1]
-      const std::vector<int>& a = trips[A];
-      const int kA = (int)a.size() - 2;
-      for (int i = 1; i <= kA; ++i) {
-        const int s = a[i];
-        const long long rem = Q(a[i - 1], s) + Q(s, a[i + 1]) - Q(a[i - 1], a[i + 1]);
-        if (!(Lq[A] - rem <= max_q)) continue;
-        for (int B = 0; B < m; ++B) {
-          const std::vector<int>& b = trips[B];
-          const int kB = (int)b.size() - 2;
-          if (B == A || kB < 1 || !(Wq[B] + qd[s] <= cap_q)) continue;
-          for (int j = 0; j <= kB; ++j) {
-            const long long ins = Q(b[j], s) + Q(s, b[j + 1]) - Q(b[j], b[j + 1]);
-            if (rem - ins > bg && Lq[B] + ins <= max_q) { bg = rem - ins; bt = 0; bA = A; bi = i; bB = B; bj = j; }
-          }
-        }
-      }
-    }
-    for (int A = 0; A < m; ++A) {  // type 1: a[i] and b[j] change places, A < B
-      const std::vector<int>& a = trips[A];
-      const int kA = (int)a.size() - 2;
-      for (int i = 1; i <= kA; ++i) {
-        const int s = a[i];
-        const long long na = Q(a[i - 1], s) + Q(s, a[i + 1]);
-        for (int B = A + 1; B < m; ++B) {
-          const std::vector<int>& b = trips[B];
-          const int kB = (int)b.size() - 2;
-          for (int j = 1; j <= kB; ++j) {
-            const int u = b[j];
-            const long long dA = Q(a[i - 1], u) + Q(u, a[i + 1]) - na;
-            const long long dB = Q(b[j - 1], s) + Q(s, b[j + 1]) - Q(b[j - 1], u) - Q(u, b[j + 1]);
-            if (-(dA + dB) > bg && Wq[A] - qd[s] + qd[u] <= cap_q && Wq[B] - qd[u] + qd[s] <= cap_q &&
-                Lq[A] + dA <= max_q && Lq[B] + dB <= max_q) {
-              bg = -(dA + dB); bt = 1; bA = A; bi = i; bB = B; bj = j;
-            }
-          }
-        }
-      }
-    }
-    if (bg <= 0) break;
-    std::vector<int> sa = trips[bA], sb = trips[bB];
-    if (bt == 0) {
-      const int s = trips[bA][bi];
-      trips[bA].erase(trips[bA].begin() + bi);
-      trips[bB].insert(trips[bB].begin() + bj + 1, s);
-    } else {
-      std::swap(trips[bA][bi], trips[bB][bj]);
-    }
-    if (!(walks(trips[bA]) && walks(trips[bB]))) {
-      trips[bA].swap(sa);
-      trips[bB].swap(sb);
-      st.rejected = 1;
-      break;
-    }
-    for (int t : {bA, bB}) {
-      Lq[t] = length(trips[t]);
-      Wq[t] = 0;
-      for (size_t p = 1; p + 1 < trips[t].size(); ++p) Wq[t] += qd[trips[t][p]];
-    }
-    ++st.moves;
-  }
-  std::vector<std::vector<int>> out;
-  st.len_after_q = 0;
-  for (auto& t : trips)
-    if (t.size() > 2) {
-      st.len_after_q += length(t);
-      out.push_back(std::move(t));
-    }
-  trips.swap(out);
-  st.trips_after = (long long)trips.size();
-  return st;
-}
-
-// The pipeline of an "exchange" request on the greedy's trips (exchange.py improve_exchange_trips).
-inline ImproveStats improve_exchange_trips(const std::vector<double>& d, int n1, const std::vector<double>& dem,
-                                           double cap, double maxd, std::vector<std::vector<int>>& trips) {
-  const ImproveStats s1 = improve_trips(d, n1, maxd, trips);
-  const ExchangeStats s2 = exchange_trips(d, n1, dem, cap, maxd, trips);
-  const ImproveStats s3 = improve_trips(d, n1, maxd, trips);
-  ImproveStats st;
-  st.exchange = true;
-  st.moves = s1.moves + s3.moves;
-  st.exchange_moves = s2.moves;
-  st.trips_before = s2.trips_before;
-  st.trips_after = s2.trips_after;
-  st.len_before_q = s1.len_before_q;
-  st.len_after_q = s3.len_after_q;
-  return st;
-}
-
-// ------------------------------------------------------------------ time windows (timewindows.py)
-// Cheapest-insertion construction of trips whose stops carry time windows and service times; the
-// definition is in routest_amd/routing/timewindows.py and this follows it step for step, so the two
-// (and K6d, csrc/route_tw.hip) agree exactly.  No floats outside the two acceptance walks and the
-// alone-feasibility test.
-constexpr long long kTwUsableLimit = 2147483647LL;  // entries of q / qt from here on are unusable
-
-struct TwStats {
-  long long insertions = 0, rejected = 0, trips = 0, len_q = 0, waiting_q = 0;
-};
-
-inline long long tw_q(double x) {
-  const long long v = improve_q(x);
-  return v >= kTwUsableLimit ? kImproveBig : v;
-}
-
-// d, t: n1 x n1 metres / seconds over [depot] + stops; dem, open, close, sv per point (index 0
-// ignored).  Returns false with the failing stops (0-based destination indices, ascending) when a
-// stop cannot be served by a trip of its own; else the trips and, per trip, the arrival and start
-// milliseconds of its stops.  n1 - 1 <= 128.
-inline bool tw_trips(const std::vector<double>& d, const std::vector<double>& t, int n1,
-                     const std::vector<double>& dem, double cap, double maxd,
-                     const std::vector<long long>& open, const std::vector<long long>& close,
-                     const std::vector<long long>& sv, std::vector<std::vector<int>>& trips,
-                     std::vector<std::vector<long long>>& arrival, std::vector<std::vector<long long>>& start,
-                     std::vector<int>& infeasible, TwStats& st) {
-  trips.clear();
-  arrival.clear();
-  start.clear();
-  infeasible.clear();
-  st = TwStats();
-  std::vector<long long> q((size_t)n1 * n1), qt((size_t)n1 * n1), qd(n1, 0);
-  for (size_t x = 0; x < q.size(); ++x) {
-    q[x] = tw_q(d[x]);
-    qt[x] = tw_q(t[x]);
-  }
-  auto Q = [&](int a, int b) { return q[(size_t)a * n1 + b]; };
-  auto T = [&](int a, int b) { return qt[(size_t)a * n1 + b]; };
-  for (int s = 1; s < n1; ++s) qd[s] = improve_q(dem[s]);
-  long long cap_q = -1, max_q = -1;
-  if (!exchange_limit(cap, cap_q)) cap_q = -1;
-  if (!exchange_limit(maxd, max_q)) max_q = -1;
-  for (int s = 1; s < n1; ++s) {
-    bool ok = dem[s] <= cap && (0.0 + (d[s] + d[(size_t)s * n1])) <= maxd;
-    ok = ok && Q(0, s) < kImproveBig && Q(s, 0) < kImproveBig && T(0, s) < kImproveBig && T(s, 0) < kImproveBig;
-    ok = ok && std::max(T(0, s), open[s]) <= close[s];
-    if (!ok) infeasible.push_back(s - 1);
-  }
-  if (!infeasible.empty()) return false;
-  std::vector<char> unrouted(n1, 1);
-  int left = n1 - 1;
-  std::vector<long long> dep, z;
-  std::vector<int> trip, cand;
-  while (left > 0) {
-    int seed = -1;
-    for (int s = 1; s < n1; ++s)
-      if (unrouted[s] && (seed < 0 || close[s] < close[seed])) seed = s;
-    trip.assign({0, seed, 0});
-    unrouted[seed] = 0;
-    --left;
-    long long Lq = Q(0, seed) + Q(seed, 0), Wq = qd[seed];
-    for (;;) {
-      const int k = (int)trip.size() - 2;
-      dep.assign(k + 1, 0);
-      z.assign(k + 2, 0);
-      for (int i = 1; i <= k; ++i)
-        dep[i] = std::max(dep[i - 1] + T(trip[i - 1], trip[i]), open[trip[i]]) + sv[trip[i]];
-      z[k] = close[trip[k]];
-      for (int i = k - 1; i >= 1; --i)
-        z[i] = std::min(close[trip[i]], z[i + 1] - T(trip[i], trip[i + 1]) - sv[trip[i]]);
-      long long bi = 0;
-      int bu = -1, bj = -1;
-      for (int u = 1; u < n1; ++u) {
-        if (!unrouted[u] || !(Wq + qd[u] <= cap_q)) continue;
-        for (int j = 0; j <= k; ++j) {
-          const int a = trip[j], b = trip[j + 1];
-          const long long qau = Q(a, u), qub = Q(u, b), tau = T(a, u), tub = T(u, b);
-          if (qau >= kImproveBig || qub >= kImproveBig || tau >= kImproveBig || tub >= kImproveBig) continue;
-          const long long ins = qau + qub - Q(a, b);
-          const long long s0 = std::max(dep[j] + tau, open[u]);
-          if (s0 > close[u] || !(j == k || s0 + sv[u] + tub <= z[j + 1]) || !(Lq + ins <= max_q)) continue;
-          if (bu < 0 || ins < bi) { bi = ins; bu = u; bj = j; }
-        }
-      }
-      if (bu < 0) break;
-      cand = trip;
-      cand.insert(cand.begin() + bj + 1, bu);
-      {  // the greedy's own f64 accumulations over the lengthened trip
-        const int kk = k + 1;
-        double s = 0.0, load = 0.0;
-        for (int p = 0; p < kk; ++p) s += d[(size_t)cand[p] * n1 + cand[p + 1]];
-        for (int p = 1; p <= kk; ++p) load += dem[cand[p]];
-        if (!(s + d[(size_t)cand[kk] * n1] <= maxd && load <= cap)) {
-          ++st.rejected;
-          break;
-        }
-      }
-      trip.swap(cand);
-      unrouted[bu] = 0;
-      --left;
-      Lq += bi;
-      Wq += qd[bu];
-      ++st.insertions;
-    }
-    const int k = (int)trip.size() - 2;
-    std::vector<long long> arr(k), sta(k);
-    long long dp = 0;
-    for (int i = 1; i <= k; ++i) {
-      arr[i - 1] = dp + T(trip[i - 1], trip[i]);
-      sta[i - 1] = std::max(arr[i - 1], open[trip[i]]);
-      dp = sta[i - 1] + sv[trip[i]];
-      st.waiting_q += sta[i - 1] - arr[i - 1];
-    }
-    st.len_q += Lq;
-    trips.push_back(trip);
-    arrival.push_back(std::move(arr));
-    start.push_back(std::move(sta));
-  }
-  st.trips = (long long)trips.size();
-  return true;
-}
-
-// ------------------------------------------------------------------ pickup-and-delivery pairs (shipments.py)
-// Cheapest insertion of units (plain stops and pickup -> delivery pairs) under time windows, with
-// the load as a profile along the trip; the definition is in routest_amd/routing/shipments.py and
-// this follows it step for step, so the two (and K6f, csrc/route_pd.hip) agree exactly.
-constexpr int kPdPlain = 0, kPdPickup = 1, kPdDelivery = 2;
-
-// kind / mate per point from pickup_from (the point index of a delivery's pickup, negative: none);
-// false on a malformed entry
-inline bool pd_kinds(const std::vector<int>& pickup_from, int n1, std::vector<int>& kind, std::vector<int>& mate) {
-  kind.assign(n1, kPdPlain);
-  mate.assign(n1, 0);
-  if ((int)pickup_from.size() != n1) return false;
-  for (int v = 1; v < n1; ++v) {
-    const int p = pickup_from[v];
-    if (p < 0) continue;
-    if (p < 1 || p >= n1 || p == v) return false;
-    kind[v] = kPdDelivery;
-    mate[v] = p;
-  }
-  for (int v = 1; v < n1; ++v) {
-    if (kind[v] != kPdDelivery) continue;
-    const int p = mate[v];
-    if (kind[p] != kPdPlain) return false;  // itself a delivery, or the pickup of another one
-    kind[p] = kPdPickup;
-    mate[p] = v;
-  }
-  return true;
-}
-
-// the f64 load walk over a trip 0, s1..sk, 0: adds and subtracts only, in this order
-inline bool pd_load_feasible(const std::vector<double>& dem, const std::vector<int>& kind,
-                             const std::vector<int>& mate, const std::vector<int>& trip, double cap) {
-  double base = 0.0;
-  for (size_t x = 1; x + 1 < trip.size(); ++x)
-    if (kind[trip[x]] == kPdPlain) base += dem[trip[x]];
-  bool ok = base <= cap;
-  double load = base;
-  for (size_t x = 1; x + 1 < trip.size(); ++x) {
-    const int s = trip[x];
-    if (kind[s] == kPdPickup) {
-      load += dem[mate[s]];
-      ok = ok && load <= cap;
-    } else {
-      load -= dem[s];
-    }
-  }
-  return ok;
-}
-
-// Inputs as tw_trips takes them, and kind / mate from pd_kinds.  n1 - 1 <= 128.
-inline bool pd_trips(const std::vector<double>& d, const std::vector<double>& t, int n1,
-                     const std::vector<double>& dem, double cap, double maxd,
-                     const std::vector<long long>& open, const std::vector<long long>& close,
-                     const std::vector<long long>& sv, const std::vector<int>& kind, const std::vector<int>& mate,
-                     std::vector<std::vector<int>>& trips, std::vector<std::vector<long long>>& arrival,
-                     std::vector<std::vector<long long>>& start, std::vector<int>& infeasible, TwStats& st) {
-  trips.clear();
-  arrival.clear();
-  start.clear();
-  infeasible.clear();
-  st = TwStats();
-  std::vector<long long> q((size_t)n1 * n1), qt((size_t)n1 * n1), qd(n1, 0);
-  for (size_t x = 0; x < q.size(); ++x) {
-    q[x] = tw_q(d[x]);
-    qt[x] = tw_q(t[x]);
-  }
-  auto Q = [&](int a, int b) { return q[(size_t)a * n1 + b]; };
-  auto T = [&](int a, int b) { return qt[(size_t)a * n1 + b]; };
-  auto usable = [&](int a, int b) { return Q(a, b) < kImproveBig && T(a, b) < kImproveBig; };
-  auto walk = [&](const std::vector<int>& tr) {  // the greedy's own f64 length
-    const int kk = (int)tr.size() - 2;
-    double s = 0.0;
-    for (int p = 0; p < kk; ++p) s += d[(size_t)tr[p] * n1 + tr[p + 1]];
-    return s + d[(size_t)tr[kk] * n1] <= maxd;
-  };
-  for (int s = 1; s < n1; ++s) qd[s] = improve_q(dem[s]);
-  long long cap_q = -1, max_q = -1;
-  if (!exchange_limit(cap, cap_q)) cap_q = -1;
-  if (!exchange_limit(maxd, max_q)) max_q = -1;
-  for (int s = 1; s < n1; ++s) {
-    if (kind[s] == kPdPlain) {
-      bool ok = dem[s] <= cap && (0.0 + (d[s] + d[(size_t)s * n1])) <= maxd;
-      ok = ok && usable(0, s) && usable(s, 0);
-      ok = ok && std::max(T(0, s), open[s]) <= close[s];
-      if (!ok) infeasible.push_back(s - 1);
-    } else if (kind[s] == kPdPickup) {
-      const int v = mate[s];
-      const std::vector<int> tr = {0, s, v, 0};
-      bool ok = walk(tr) && pd_load_feasible(dem, kind, mate, tr, cap);
-      ok = ok && usable(0, s) && usable(s, v) && usable(v, 0);
-      if (ok) {
-        const long long sp = std::max(T(0, s), open[s]);
-        const long long s2 = std::max(sp + sv[s] + T(s, v), open[v]);
-        ok = sp <= close[s] && s2 <= close[v];
-      }
-      if (!ok) {
-        infeasible.push_back(s - 1);
-        infeasible.push_back(v - 1);
-      }
-    }
-  }
-  if (!infeasible.empty()) {
-    std::sort(infeasible.begin(), infeasible.end());
-    return false;
-  }
-  std::vector<char> unrouted(n1, 1);
-  int left = n1 - 1;
-  std::vector<long long> dep, z, load;
-  std::vector<int> trip, cand;
-  while (left > 0) {
-    int seed = -1;
-    long long key = 0;
-    for (int u = 1; u < n1; ++u) {
-      if (!unrouted[u] || kind[u] == kPdDelivery) continue;
-      const long long ku = kind[u] == kPdPlain ? close[u] : std::min(close[u], close[mate[u]]);
-      if (seed < 0 || ku < key) { seed = u; key = ku; }
-    }
-    if (kind[seed] == kPdPlain) trip.assign({0, seed, 0});
-    else trip.assign({0, seed, mate[seed], 0});
-    for (size_t x = 1; x + 1 < trip.size(); ++x) { unrouted[trip[x]] = 0; --left; }
-    long long Lq = 0;
-    for (size_t x = 0; x + 1 < trip.size(); ++x) Lq += Q(trip[x], trip[x + 1]);
-    for (;;) {
-      const int k = (int)trip.size() - 2;
-      dep.assign(k + 1, 0);
-      z.assign(k + 2, 0);
-      load.assign(k + 1, 0);
-      for (int i = 1; i <= k; ++i)
-        dep[i] = std::max(dep[i - 1] + T(trip[i - 1], trip[i]), open[trip[i]]) + sv[trip[i]];
-      z[k] = close[trip[k]];
-      for (int i = k - 1; i >= 1; --i)
-        z[i] = std::min(close[trip[i]], z[i + 1] - T(trip[i], trip[i + 1]) - sv[trip[i]]);
-      for (int i = 1; i <= k; ++i)
-        if (kind[trip[i]] == kPdPlain) load[0] += qd[trip[i]];
-      for (int i = 1; i <= k; ++i)
-        load[i] = kind[trip[i]] == kPdPickup ? load[i - 1] + qd[mate[trip[i]]] : load[i - 1] - qd[trip[i]];
-      long long bi = 0;
-      int bu = -1, bp = -1, bj = -1;
-      auto offer = [&](long long ins, int u, int i, int j) {  // in (u, i, j) order: a strict < keeps the first
-        if (!(Lq + ins <= max_q)) return;
-        if (bu < 0 || ins < bi) { bi = ins; bu = u; bp = i; bj = j; }
-      };
-      for (int u = 1; u < n1; ++u) {
-        if (!unrouted[u] || kind[u] == kPdDelivery) continue;
-        const int v = mate[u];
-        const long long amt = qd[v];
-        long long pm = LLONG_MIN;
-        for (int i = 0; i <= k; ++i) {
-          pm = std::max(pm, load[i]);
-          const int a = trip[i], b = trip[i + 1];
-          if (!usable(a, u)) continue;
-          const long long s0 = std::max(dep[i] + T(a, u), open[u]);
-          if (s0 > close[u]) continue;
-          if (kind[u] == kPdPlain) {
-            if (!usable(u, b) || !(pm + qd[u] <= cap_q)) continue;
-            if (!(i == k || s0 + sv[u] + T(u, b) <= z[i + 1])) continue;
-            offer(Q(a, u) + Q(u, b) - Q(a, b), u, i, i);
-            continue;
-          }
-          // j == i: a -> p -> v -> b
-          if (usable(u, v) && usable(v, b) && load[i] + amt <= cap_q) {
-            const long long s2 = std::max(s0 + sv[u] + T(u, v), open[v]);
-            if (s2 <= close[v] && (i == k || s2 + sv[v] + T(v, b) <= z[i + 1]))
-              offer(Q(a, u) + Q(u, v) + Q(v, b) - Q(a, b), u, i, i);
-          }
-          // j > i: the departures behind p, shifted, carried forward
-          if (i == k || !usable(u, b)) continue;
-          const long long first = s0 + sv[u] + T(u, b);
-          if (first > z[i + 1]) continue;
-          const long long ins1 = Q(a, u) + Q(u, b) - Q(a, b);
-          long long nd = std::max(first, open[b]) + sv[b], mx = load[i];
-          for (int j = i + 1; j <= k; ++j) {
-            const int c = trip[j], e = trip[j + 1];
-            if (j > i + 1) nd = std::max(nd + T(trip[j - 1], c), open[c]) + sv[c];
-            mx = std::max(mx, load[j]);
-            if (!usable(c, v) || !usable(v, e) || !(mx + amt <= cap_q)) continue;
-            const long long s2 = std::max(nd + T(c, v), open[v]);
-            if (s2 > close[v] || !(j == k || s2 + sv[v] + T(v, e) <= z[j + 1])) continue;
-            offer(ins1 + (Q(c, v) + Q(v, e) - Q(c, e)), u, i, j);
-          }
-        }
-      }
-      if (bu < 0) break;
-      cand = trip;
-      if (kind[bu] == kPdPickup) cand.insert(cand.begin() + bj + 1, mate[bu]);
-      cand.insert(cand.begin() + bp + 1, bu);
-      if (!(walk(cand) && pd_load_feasible(dem, kind, mate, cand, cap))) {
-        ++st.rejected;
-        break;
-      }
-      trip.swap(cand);
-      unrouted[bu] = 0;
-      --left;
-      if (kind[bu] == kPdPickup) { unrouted[mate[bu]] = 0; --left; }
-      Lq += bi;
-      ++st.insertions;
-    }
-    const int k = (int)trip.size() - 2;
-    std::vector<long long> arr(k), sta(k);
-    long long dp = 0;
-    for (int i = 1; i <= k; ++i) {
-      arr[i - 1] = dp + T(trip[i - 1], trip[i]);
-      sta[i - 1] = std::max(arr[i - 1], open[trip[i]]);
-      dp = sta[i - 1] + sv[trip[i]];
-      st.waiting_q += sta[i - 1] - arr[i - 1];
-    }
-    st.len_q += Lq;
-    trips.push_back(trip);
-    arrival.push_back(std::move(arr));
-    start.push_back(std::move(sta));
-  }
-  st.trips = (long long)trips.size();
-  return true;
-}
-
-// ------------------------------------------------------------------ window-aware local search (tw_improve.py)
-// Best-improvement relocate (between trips and inside one) and swap of single stops on tw_trips'
-// output, under the windows, the service times, the capacity and the distance limit; the definition
-// is in routest_amd/routing/tw_improve.py and this follows it move for move, so the two (and K6e,
-// csrc/route_tw_improve.hip) agree exactly.
-struct TwImproveStats {
-  long long moves = 0, rejected = 0, trips_before = 0, trips_after = 0, len_before_q = 0, len_after_q = 0,
-            waiting_q = 0;
-};
-
-// Inputs as tw_trips takes them; trips [0, ..., 0] over the stops, all time-feasible, rewritten in
-// place (emptied trips dropped); arrival / start: the schedule of the trips that come out.
-inline TwImproveStats tw_improve_trips(const std::vector<double>& d, const std::vector<double>& t, int n1,
-                                       const std::vector<double>& dem, double cap, double maxd,
-                                       const std::vector<long long>& open, const std::vector<long long>& close,
-                                       const std::vector<long long>& sv, std::vector<std::vector<int>>& trips,
-                                       std::vector<std::vector<long long>>& arrival,
-                                       std::vector<std::vector<long long>>& start) {
-  TwImproveStats st;
-  const int ns = n1 - 1, m = (int)trips.size();
-  std::vector<long long> q((size_t)n1 * n1), qt((size_t)n1 * n1), qd(n1, 0);
-  for (size_t x = 0; x < q.size(); ++x) {
-    q[x] = tw_q(d[x]);
-    qt[x] = tw_q(t[x]);
-  }
-  auto Q = [&](int a, int b) { return q[(size_t)a * n1 + b]; };
-  auto T = [&](int a, int b) { return qt[(size_t)a * n1 + b]; };
-  auto usable = [&](int a, int b) { return Q(a, b) < kImproveBig && T(a, b) < kImproveBig; };
-  auto op = [&](int s) { return s == 0 ? 0LL : open[s]; };
-  auto cl = [&](int s) { return s == 0 ? kExchangeUnbounded : close[s]; };
-  auto svc = [&](int s) { return s == 0 ? 0LL : sv[s]; };
-  bool skip = ns > kImproveMaxStops;
-  for (int s = 1; s < n1; ++s) {
-    qd[s] = improve_q(dem[s]);
-    skip = skip || qd[s] == kImproveBig;
-  }
-  long long cap_q = -1, max_q = -1;
-  if (!exchange_limit(cap, cap_q)) cap_q = -1;
-  if (!exchange_limit(maxd, max_q)) max_q = -1;
-  skip = skip || cap_q < 0 || max_q < 0;
-  std::vector<long long> Lq(m, 0), Wq(m, 0);
-  std::vector<std::vector<long long>> dep(m), z(m);
-  auto refresh = [&](int x) {
-    const std::vector<int>& tr = trips[x];
-    const int k = (int)tr.size() - 2;
-    Lq[x] = Wq[x] = 0;
-    dep[x].assign(k > 0 ? k + 1 : 1, 0);
-    z[x].assign(k > 0 ? k + 2 : 2, 0);
-    if (k < 1) return;
-    for (int p = 0; p <= k; ++p) Lq[x] += Q(tr[p], tr[p + 1]);
-    for (int i = 1; i <= k; ++i) {
-      Wq[x] += qd[tr[i]];
-      dep[x][i] = std::max(dep[x][i - 1] + T(tr[i - 1], tr[i]), op(tr[i])) + svc(tr[i]);
-    }
-    z[x][k] = cl(tr[k]);
-    for (int i = k - 1; i >= 1; --i) z[x][i] = std::min(cl(tr[i]), z[x][i + 1] - T(tr[i], tr[i + 1]) - svc(tr[i]));
-  };
-  for (int x = 0; x < m; ++x) {
-    refresh(x);
-    st.len_before_q += Lq[x];
-  }
-  st.trips_before = m;
-  // the greedy's own f64 accumulations over one trip
-  auto walks = [&](const std::vector<int>& tr) {
-    const int k = (int)tr.size() - 2;
-    if (k < 1) return true;
-    double s = 0.0, load = 0.0;
-    for (int p = 0; p < k; ++p) s += d[(size_t)tr[p] * n1 + tr[p + 1]];
-    for (int p = 1; p <= k; ++p) load += dem[tr[p]];
-    return s + d[(size_t)tr[k] * n1] <= maxd && load <= cap;
-  };
-  std::vector<int> na;
-  while (!skip && st.moves < 4LL * ns) {
-    long long bg = 0;
-    int bt = -1, bA = -1, bi = -1, bB = -1, bj = -1;
-    for (int A = 0; A < m; ++A) {  // type 0: a[i] goes between b[j] and b[j+1]
-      const std::vector<int>& a = trips[A];
-      const int kA = (int)a.size() - 2;
-      for (int i = 1; i <= kA; ++i) {
-        const int p = a[i - 1], s = a[i], n = a[i + 1];
-        const long long rem = kA == 1 ? Q(0, s) + Q(s, 0) : Q(p, s) + Q(s, n) - Q(p, n);
-        if (!(kA == 1 || usable(p, n)) || !(Lq[A] - rem <= max_q)) continue;
-        if (!(kA == 1 || i == kA || std::max(dep[A][i - 1] + T(p, n), op(n)) <= z[A][i + 1])) continue;
-        for (int B = 0; B < m; ++B) {
-          const std::vector<int>& b = trips[B];
-          const int kB = (int)b.size() - 2;
-          if (B == A || kB < 1 || !(Wq[B] + qd[s] <= cap_q)) continue;
-          for (int j = 0; j <= kB; ++j) {
-            const int u = b[j], v = b[j + 1];
-            if (!usable(u, s) || !usable(s, v)) continue;
-            const long long ins = Q(u, s) + Q(s, v) - Q(u, v);
-            if (!(rem - ins > bg) || !(Lq[B] + ins <= max_q)) continue;
-            const long long s0 = std::max(dep[B][j] + T(u, s), op(s));
-            if (s0 > cl(s) || !(j == kB || s0 + svc(s) + T(s, v) <= z[B][j + 1])) continue;
-            bg = rem - ins; bt = 0; bA = A; bi = i; bB = B; bj = j;
-          }
-        }
-      }
-    }
-    for (int A = 0; A < m; ++A) {  // type 1: a[i] and b[j] change places, A < B
-      const std::vector<int>& a = trips[A];
-      const int kA = (int)a.size() - 2;
-      for (int i = 1; i <= kA; ++i) {
-        const int p = a[i - 1], s = a[i], n = a[i + 1];
-        const long long nba = Q(p, s) + Q(s, n);
-        for (int B = A + 1; B < m; ++B) {
-          const std::vector<int>& b = trips[B];
-          const int kB = (int)b.size() - 2;
-          for (int j = 1; j <= kB; ++j) {
-            const int u = b[j], pb = b[j - 1], nb = b[j + 1];
-            if (!usable(p, u) || !usable(u, n) || !usable(pb, s) || !usable(s, nb)) continue;
-            const long long dA = Q(p, u) + Q(u, n) - nba;
-            const long long dB = Q(pb, s) + Q(s, nb) - Q(pb, u) - Q(u, nb);
-            if (!(-(dA + dB) > bg) || !(Wq[A] - qd[s] + qd[u] <= cap_q) || !(Wq[B] - qd[u] + qd[s] <= cap_q) ||
-                !(Lq[A] + dA <= max_q) || !(Lq[B] + dB <= max_q))
-              continue;
-            const long long su = std::max(dep[A][i - 1] + T(p, u), op(u));
-            if (su > cl(u) || !(i == kA || su + svc(u) + T(u, n) <= z[A][i + 1])) continue;
-            const long long ss = std::max(dep[B][j - 1] + T(pb, s), op(s));
-            if (ss > cl(s) || !(j == kB || ss + svc(s) + T(s, nb) <= z[B][j + 1])) continue;
-            bg = -(dA + dB); bt = 1; bA = A; bi = i; bB = B; bj = j;
-          }
-        }
-      }
-    }
-    for (int A = 0; A < m; ++A) {  // type 2: a[i] goes between a[j] and a[j+1] of its own trip
-      const std::vector<int>& a = trips[A];
-      const int kA = (int)a.size() - 2;
-      if (kA < 2) continue;
-      for (int i = 1; i <= kA; ++i) {
-        const int p = a[i - 1], s = a[i], n = a[i + 1];
-        if (!usable(p, n)) continue;
-        const long long rem = Q(p, s) + Q(s, n) - Q(p, n);
-        for (int j = 0; j <= kA; ++j) {
-          if (j == i - 1 || j == i) continue;
-          const int u = a[j], v = a[j + 1];
-          if (!usable(u, s) || !usable(s, v)) continue;
-          const long long gain = rem - (Q(u, s) + Q(s, v) - Q(u, v));
-          if (!(gain > bg) || !(Lq[A] - gain <= max_q)) continue;
-          na = a;
-          na.erase(na.begin() + i);
-          na.insert(na.begin() + (j < i ? j + 1 : j), s);
-          const int lo = std::min(i, j + 1), hi = std::max(i, j);
-          long long clock = dep[A][lo - 1];
-          bool ok = true;
-          for (int x = lo; x <= hi && ok; ++x) {
-            const long long s0 = std::max(clock + T(na[x - 1], na[x]), op(na[x]));
-            ok = s0 <= cl(na[x]);
-            clock = s0 + svc(na[x]);
-          }
-          if (ok && hi < kA) ok = std::max(clock + T(na[hi], na[hi + 1]), op(na[hi + 1])) <= z[A][hi + 1];
-          if (!ok) continue;
-          bg = gain; bt = 2; bA = A; bi = i; bB = A; bj = j;
-        }
-      }
-    }
-    if (bg <= 0) break;
-    std::vector<int> sa = trips[bA], sb = trips[bB];
-    const int s = trips[bA][bi];
-    if (bt == 0) {
-      trips[bA].erase(trips[bA].begin() + bi);
-      trips[bB].insert(trips[bB].begin() + bj + 1, s);
-    } else if (bt == 1) {
-      std::swap(trips[bA][bi], trips[bB][bj]);
-    } else {
-      trips[bA].erase(trips[bA].begin() + bi);
-      trips[bA].insert(trips[bA].begin() + (bj < bi ? bj + 1 : bj), s);
-    }
-    if (!(walks(trips[bA]) && walks(trips[bB]))) {
-      if (bt == 2) {
-        trips[bA].swap(sa);
-      } else {
-        trips[bA].swap(sa);
-        trips[bB].swap(sb);
-      }
-      st.rejected = 1;
-      break;
-    }
-    refresh(bA);
-    refresh(bB);
-    ++st.moves;
-  }
-  std::vector<std::vector<int>> out;
-  arrival.clear();
-  start.clear();
-  for (int x = 0; x < m; ++x) {
-    std::vector<int>& tr = trips[x];
-    const int k = (int)tr.size() - 2;
-    if (k < 1) continue;
-    st.len_after_q += Lq[x];
-    std::vector<long long> arr(k), sta(k);
-    long long dp = 0;
-    for (int i = 1; i <= k; ++i) {
-      arr[i - 1] = dp + T(tr[i - 1], tr[i]);
-      sta[i - 1] = std::max(arr[i - 1], op(tr[i]));
-      dp = sta[i - 1] + svc(tr[i]);
-      st.waiting_q += sta[i - 1] - arr[i - 1];
-    }
-    out.push_back(std::move(tr));
-    arrival.push_back(std::move(arr));
-    start.push_back(std::move(sta));
-  }
-  trips.swap(out);
-  st.trips_after = (long long)trips.size();
-  return st;
-}
-
-// ------------------------------------------------------------------ unit relocate on shipment trips (shipment_improve.py)
-// Best-improvement relocation of whole units (a plain stop, or a pickup -> delivery pair) on
-// pd_trips' output, into another trip or inside their own; the definition is in
-// routest_amd/routing/shipment_improve.py and this follows it move for move, so the two (and K6g,
-// csrc/route_pd_improve.hip) agree exactly.
-struct PdImproveStats {
-  long long moves = 0, pair_moves = 0, rejected = 0, trips_before = 0, trips_after = 0, len_before_q = 0,
-            len_after_q = 0, waiting_q = 0;
-};
-struct PdMove {
-  int type, A, x, B, i, j;
-};
-
-// Inputs as pd_trips takes them; trips [0, ..., 0] as it returns them, rewritten in place (emptied
-// trips dropped); arrival / start: the schedule of the trips that come out.  applied: receives every
-// move that is kept (the self-test re-simulates them).
-inline PdImproveStats pd_improve_trips(const std::vector<double>& d, const std::vector<double>& t, int n1,
-                                       const std::vector<double>& dem, double cap, double maxd,
-                                       const std::vector<long long>& open, const std::vector<long long>& close,
-                                       const std::vector<long long>& sv, const std::vector<int>& kind,
-                                       const std::vector<int>& mate, std::vector<std::vector<int>>& trips,
-                                       std::vector<std::vector<long long>>& arrival,
-                                       std::vector<std::vector<long long>>& start,
-                                       std::vector<PdMove>* applied = nullptr) {
-  PdImproveStats st;
-  const int ns = n1 - 1, m = (int)trips.size();
-  std::vector<long long> q((size_t)n1 * n1), qt((size_t)n1 * n1), qd(n1, 0);
-  for (size_t x = 0; x < q.size(); ++x) {
-    q[x] = tw_q(d[x]);
-    qt[x] = tw_q(t[x]);
-  }
-  auto Q = [&](int a, int b) { return q[(size_t)a * n1 + b]; };
-  auto T = [&](int a, int b) { return qt[(size_t)a * n1 + b]; };
-  auto usable = [&](int a, int b) { return Q(a, b) < kImproveBig && T(a, b) < kImproveBig; };
-  auto op = [&](int s) { return s == 0 ? 0LL : open[s]; };
-  auto cl = [&](int s) { return s == 0 ? kExchangeUnbounded : close[s]; };
-  auto svc = [&](int s) { return s == 0 ? 0LL : sv[s]; };
-  bool skip = ns > kImproveMaxStops;
-  for (int s = 1; s < n1; ++s) {
-    qd[s] = improve_q(dem[s]);
-    skip = skip || (qd[s] == kImproveBig && kind[s] != kPdPickup);
-  }
-  long long cap_q = -1, max_q = -1;
-  if (!exchange_limit(cap, cap_q)) cap_q = -1;
-  if (!exchange_limit(maxd, max_q)) max_q = -1;
-  skip = skip || cap_q < 0 || max_q < 0;
-  // one walk of a trip: its millimetre length (0 for an empty one) and whether its legs are usable,
-  // its schedule is feasible and its load stays within cap_q
-  auto sound = [&](const std::vector<int>& tr, long long& len) {
-    const int k = (int)tr.size() - 2;
-    len = 0;
-    if (k < 1) return true;
-    bool ok = true;
-    long long ld = 0, clock = 0;
-    for (int i = 1; i <= k; ++i)
-      if (kind[tr[i]] == kPdPlain) ld += qd[tr[i]];
-    ok = ld <= cap_q;
-    for (int i = 1; i <= k + 1; ++i) {
-      const int a = tr[i - 1], b = tr[i];
-      len += Q(a, b);
-      ok = ok && usable(a, b);
-      if (i > k) break;
-      const long long s0 = std::max(clock + T(a, b), op(b));
-      ok = ok && s0 <= cl(b);
-      clock = s0 + svc(b);
-      ld += kind[b] == kPdPickup ? qd[mate[b]] : -qd[b];
-      ok = ok && ld <= cap_q;
-    }
-    return ok;
-  };
-  auto without = [&](const std::vector<int>& tr, int x, std::vector<int>& rest) {
-    const int u = tr[x], v = kind[u] == kPdPickup ? mate[u] : -1;
-    rest.clear();
-    for (size_t p = 0; p < tr.size(); ++p)
-      if (p == 0 || p + 1 == tr.size() || (tr[p] != u && tr[p] != v)) rest.push_back(tr[p]);
-  };
-  auto insert = [&](const std::vector<int>& tr, int u, int i, int j, std::vector<int>& out) {
-    out = tr;
-    if (kind[u] == kPdPickup) out.insert(out.begin() + j + 1, mate[u]);
-    out.insert(out.begin() + i + 1, u);
-  };
-  auto walks = [&](const std::vector<int>& tr) {  // the greedy's own f64 accumulations over one trip
-    const int k = (int)tr.size() - 2;
-    if (k < 1) return true;
-    double s = 0.0;
-    for (int p = 0; p < k; ++p) s += d[(size_t)tr[p] * n1 + tr[p + 1]];
-    return s + d[(size_t)tr[k] * n1] <= maxd && pd_load_feasible(dem, kind, mate, tr, cap);
-  };
-  std::vector<long long> Lq(m, 0);
-  std::vector<char> snd(m, 1);
-  std::vector<std::vector<long long>> dep(m), z(m), load(m);
-  auto refresh = [&](int x) {
-    const std::vector<int>& tr = trips[x];
-    const int k = (int)tr.size() - 2;
-    snd[x] = sound(tr, Lq[x]) ? 1 : 0;
-    dep[x].assign(k > 0 ? k + 1 : 1, 0);
-    z[x].assign(k > 0 ? k + 2 : 2, 0);
-    load[x].assign(k > 0 ? k + 1 : 1, 0);
-    if (k < 1) return;
-    for (int i = 1; i <= k; ++i) {
-      dep[x][i] = std::max(dep[x][i - 1] + T(tr[i - 1], tr[i]), op(tr[i])) + svc(tr[i]);
-      if (kind[tr[i]] == kPdPlain) load[x][0] += qd[tr[i]];
-    }
-    for (int i = 1; i <= k; ++i)
-      load[x][i] = kind[tr[i]] == kPdPickup ? load[x][i - 1] + qd[mate[tr[i]]] : load[x][i - 1] - qd[tr[i]];
-    z[x][k] = cl(tr[k]);
-    for (int i = k - 1; i >= 1; --i) z[x][i] = std::min(cl(tr[i]), z[x][i + 1] - T(tr[i], tr[i + 1]) - svc(tr[i]));
-  };
-  for (int x = 0; x < m; ++x) {
-    refresh(x);
-    st.len_before_q += Lq[x];
-  }
-  st.trips_before = m;
-  std::vector<int> rest, cand;
-  while (!skip && st.moves < 4LL * ns) {
-    long long bg = 0;
-    PdMove bm = {-1, -1, -1, -1, -1, -1};
-    // candidates in (type, A, x, B, i, j) order: a strict > keeps the first of equal gains
-    for (int A = 0; A < m; ++A) {  // type 0: the unit at x goes to trip B
-      const std::vector<int>& a = trips[A];
-      for (int x = 1; x + 1 < (int)a.size(); ++x) {
-        const int u = a[x];
-        if (kind[u] == kPdDelivery) continue;
-        without(a, x, rest);
-        long long rlen = 0;
-        if (!sound(rest, rlen) || !(rlen <= max_q)) continue;
-        const long long rem = Lq[A] - rlen;
-        const int v = mate[u];
-        const long long amt = qd[v];
-        for (int B = 0; B < m; ++B) {
-          const std::vector<int>& trip = trips[B];
-          const int k = (int)trip.size() - 2;
-          if (B == A || k < 1 || !snd[B]) continue;
-          auto offer = [&](long long ins, int i, int j) {
-            if (!(rem - ins > bg) || !(Lq[B] + ins <= max_q)) return;
-            bg = rem - ins;
-            bm = {0, A, x, B, i, j};
-          };
-          long long pm = LLONG_MIN;
-          for (int i = 0; i <= k; ++i) {  // pd_trips' candidates of the unit on trip B
-            pm = std::max(pm, load[B][i]);
-            const int pa = trip[i], pb = trip[i + 1];
-            if (!usable(pa, u)) continue;
-            const long long s0 = std::max(dep[B][i] + T(pa, u), op(u));
-            if (s0 > cl(u)) continue;
-            if (kind[u] == kPdPlain) {
-              if (!usable(u, pb) || !(pm + qd[u] <= cap_q)) continue;
-              if (!(i == k || s0 + svc(u) + T(u, pb) <= z[B][i + 1])) continue;
-              offer(Q(pa, u) + Q(u, pb) - Q(pa, pb), i, i);
-              continue;
-            }
-            if (usable(u, v) && usable(v, pb) && load[B][i] + amt <= cap_q) {
-              const long long s2 = std::max(s0 + svc(u) + T(u, v), op(v));
-              if (s2 <= cl(v) && (i == k || s2 + svc(v) + T(v, pb) <= z[B][i + 1]))
-                offer(Q(pa, u) + Q(u, v) + Q(v, pb) - Q(pa, pb), i, i);
-            }
-            if (i == k || !usable(u, pb)) continue;
-            const long long first = s0 + svc(u) + T(u, pb);
-            if (first > z[B][i + 1]) continue;
-            const long long ins1 = Q(pa, u) + Q(u, pb) - Q(pa, pb);
-            long long nd = std::max(first, op(pb)) + svc(pb), mx = load[B][i];
-            for (int j = i + 1; j <= k; ++j) {
-              const int c = trip[j], e = trip[j + 1];
-              if (j > i + 1) nd = std::max(nd + T(trip[j - 1], c), op(c)) + svc(c);
-              mx = std::max(mx, load[B][j]);
-              if (!usable(c, v) || !usable(v, e) || !(mx + amt <= cap_q)) continue;
-              const long long s2 = std::max(nd + T(c, v), op(v));
-              if (s2 > cl(v) || !(j == k || s2 + svc(v) + T(v, e) <= z[B][j + 1])) continue;
-              offer(ins1 + (Q(c, v) + Q(v, e) - Q(c, e)), i, j);
-            }
-          }
-        }
-      }
-    }
-    for (int A = 0; A < m; ++A) {  // type 1: the unit at x goes back into A', the rest of its trip
-      const std::vector<int>& a = trips[A];
-      for (int x = 1; x + 1 < (int)a.size(); ++x) {
-        const int u = a[x];
-        if (kind[u] == kPdDelivery) continue;
-        without(a, x, rest);
-        const int k = (int)rest.size() - 2;
-        if (k < 1) continue;
-        long long rlen = 0;
-        for (int p = 0; p <= k; ++p) rlen += Q(rest[p], rest[p + 1]);
-        const long long rem = Lq[A] - rlen;
-        const bool pair = kind[u] == kPdPickup;
-        const int v = mate[u];
-        for (int i = 0; i <= k; ++i) {
-          const int pa = rest[i], pb = rest[i + 1];
-          for (int j = i; j <= (pair ? k : i); ++j) {
-            long long ins;
-            if (!pair) {
-              ins = Q(pa, u) + Q(u, pb) - Q(pa, pb);
-            } else if (j == i) {
-              ins = Q(pa, u) + Q(u, v) + Q(v, pb) - Q(pa, pb);
-            } else {
-              const int c = rest[j], e = rest[j + 1];
-              ins = (Q(pa, u) + Q(u, pb) - Q(pa, pb)) + (Q(c, v) + Q(v, e) - Q(c, e));
-            }
-            const long long g = rem - ins;
-            if (!(g > bg) || !(Lq[A] - g <= max_q)) continue;  // the walk only where it can matter
-            insert(rest, u, i, j, cand);
-            long long len = 0;
-            if (!sound(cand, len)) continue;
-            bg = g;
-            bm = {1, A, x, A, i, j};
-          }
-        }
-      }
-    }
-    if (bg <= 0) break;
-    std::vector<int> sa = trips[bm.A], sb = trips[bm.B];
-    const int u = trips[bm.A][bm.x];
-    without(sa, bm.x, rest);
-    if (bm.type == 0) {
-      insert(sb, u, bm.i, bm.j, cand);
-      trips[bm.A] = rest;
-      trips[bm.B] = cand;
-    } else {
-      insert(rest, u, bm.i, bm.j, cand);
-      trips[bm.A] = cand;
-    }
-    if (!(walks(trips[bm.A]) && walks(trips[bm.B]))) {
-      trips[bm.A].swap(sa);
-      if (bm.type == 0) trips[bm.B].swap(sb);
-      st.rejected = 1;
-      break;
-    }
-    refresh(bm.A);
-    refresh(bm.B);
-    ++st.moves;
-    if (kind[u] == kPdPickup) ++st.pair_moves;
-    if (applied) applied->push_back(bm);
-  }
-  std::vector<std::vector<int>> out;
-  arrival.clear();
-  start.clear();
-  for (int x = 0; x < m; ++x) {
-    std::vector<int>& tr = trips[x];
-    const int k = (int)tr.size() - 2;
-    if (k < 1) continue;
-    st.len_after_q += Lq[x];
-    std::vector<long long> arr(k), sta(k);
-    long long dp = 0;
-    for (int i = 1; i <= k; ++i) {
-      arr[i - 1] = dp + T(tr[i - 1], tr[i]);
-      sta[i - 1] = std::max(arr[i - 1], op(tr[i]));
-      dp = sta[i - 1] + svc(tr[i]);
-      st.waiting_q += sta[i - 1] - arr[i - 1];
-    }
-    out.push_back(std::move(tr));
-    arrival.push_back(std::move(arr));
-    start.push_back(std::move(sta));
-  }
-  trips.swap(out);
-  st.trips_after = (long long)trips.size();
-  return st;
 }
 
 // ------------------------------------------------------------------ nearest-node snapping
